@@ -13,9 +13,17 @@ target norm and loaded into the measured engine (and, for the CPU baseline, into
 `--gpus N`: STRONG scaling -- the same global m hash-sharded over N ranks, one per MI355X, RCCL; `value` is the global
 iterations/s.  Without a launcher around it (WORLD_SIZE unset) and N > 1 the script starts its own N ranks with
 torch.distributed.run before touching a GPU; it refuses to run when fewer than N GPUs are visible or when the process group's
-size is not N.  At N == 8 (or --config4 1) BASELINE config 4 (H2O-shaped, m = 1e7 over the ranks) is timed as well (key `config4`).
+size is not N.  With --full, at N == 8 (or --config4 1) BASELINE config 4 (H2O-shaped, m = 1e7 over the ranks) is timed as well (key `config4`).
 
-Prints ONE JSON line (rank 0).  Extra keys: spawns_per_s, roofline, cpu_baseline, parity.
+A plain run sets up, warms up, times `--steps` iterations in one call and prints ONE JSON line (rank 0) with the headline
+figure, `ms_per_step` and the counters of the timed region.  `--full` adds everything that takes runs of its own: the roofline
+of the dominant kernel (HIP events over `--profile-steps` further iterations, the measured copy bandwidth), the CPU baseline
+(the reference, or the oracle port, from the same restart state), the parity leg against it, and BASELINE config 4 (`config4`).
+
+`--dump-outputs DIR` writes, after the timed steps, the vector the timed iterations left on the device as `eng.vector()` returns
+it to a caller (positions in storage order): DIR/vals.npy (float64), DIR/dets.npy (the determinants' bit strings as float64,
+exact below 2^53; wider ones as dets_lo.npy / dets_hi.npy, 32 bits each) and DIR/vec_info.npy (curr_size, n_nonz, n_free).
+Filler run, restart state and seeds are fixed, so two builds given the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -131,6 +139,31 @@ def cpu_baseline(args, mol, par, dets, vals, run_seed, m):
     return cb, {f: [x for x in lo[f]] for f in ("numer", "denom", "norm", "nkept", "n_nonz", "curr_size", "num_success")}
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, eng, rank, world):
+    """What the timed path left for its caller after the last timed step: the stored vector (determinants and values by position)."""
+    os.makedirs(dirname, exist_ok=True)
+    info = eng.vec_info()
+    dets, vals = eng.vector()
+    wide = bool(dets.size) and int(dets.max()) >= (1 << 53)
+    per_elem = 8 * (3 if wide else 2)
+    budget = DUMP_LIMIT_BYTES - 4096                         # .npy headers and vec_info
+    if dets.size * per_elem > budget:
+        # a fixed, seeded sample of the positions (sorted, so that the order of storage is kept)
+        pick = np.sort(np.random.default_rng(12345).choice(dets.size, size=budget // per_elem, replace=False))
+        dets, vals = dets[pick], vals[pick]
+    sfx = "" if world == 1 else f"_r{rank}"
+    np.save(os.path.join(dirname, f"vals{sfx}.npy"), np.ascontiguousarray(vals, dtype=np.float64))
+    if wide:
+        np.save(os.path.join(dirname, f"dets_lo{sfx}.npy"), (dets & np.uint64(0xFFFFFFFF)).astype(np.float64))
+        np.save(os.path.join(dirname, f"dets_hi{sfx}.npy"), (dets >> np.uint64(32)).astype(np.float64))
+    else:
+        np.save(os.path.join(dirname, f"dets{sfx}.npy"), dets.astype(np.float64))
+    np.save(os.path.join(dirname, f"vec_info{sfx}.npy"), np.asarray(info, dtype=np.float64))
+
+
 def run_workload(args, shape, m_glob, world, rank, device, dist, steps, warmup, primary):
     """One timed run of the frisys_mol loop on a hash-sharded vector of m_glob non-zeros over `world` ranks.  Strong scaling:
     m_glob is the GLOBAL budget (vec_nonz = mat_nonz = target), whatever the number of ranks -- the run
@@ -178,7 +211,8 @@ def run_workload(args, shape, m_glob, world, rank, device, dist, steps, warmup, 
             import torch
             torch.cuda.synchronize()
 
-    first_logs = eng.iterate(warmup) if warmup else None
+    if warmup:
+        eng.iterate(warmup)
     c0 = eng.counters()
     coll0 = comm.n_collectives() if comm is not None else 0
     barrier()
@@ -222,7 +256,9 @@ def run_workload(args, shape, m_glob, world, rank, device, dist, steps, warmup, 
     if STARTUP:
         result["startup"] = {"iterations": STARTUP["iterations"], "ms_per_iter": 1e3 * STARTUP["seconds"] / max(1, STARTUP["iterations"]),
                              "note": "filler run from the HF determinant to m determinants (initiator 0), find_keep_sub in the reference's own order where its running norm collapses (DESIGN.md section 2); not part of `value`"}
-    if not primary:
+    if primary and args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, rank, world)
+    if not primary or not args.full:
         eng.close()
         return result if rank == 0 else None
 
@@ -349,16 +385,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--m", type=int, default=int(os.environ.get("FRIES_BENCH_M", "1000000")), help="GLOBAL non-zeros (vec_nonz = mat_nonz = target), fixed as N grows")
     ap.add_argument("--shape", default="N2")
-    ap.add_argument("--cpu-iters", type=int, default=-1, help="oracle iterations for cpu_baseline (-1: sized to ~20 s; 0: skip)")
-    ap.add_argument("--profile-steps", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: roofline of the dominant kernel, CPU baseline, parity against it, config 4")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the vector the last timed step left (vals, dets, vec_info) as DIR/<name>.npy")
+    ap.add_argument("--cpu-iters", type=int, default=-1, help="with --full: oracle iterations for cpu_baseline (-1: sized to ~20 s; 0: skip)")
+    ap.add_argument("--profile-steps", type=int, default=5, help="with --full: iterations timed kernel by kernel for the roofline")
     ap.add_argument("--backend", default=os.environ.get("FRIES_BENCH_BACKEND", "nccl"), help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--transport", default=os.environ.get("FRIES_BENCH_TRANSPORT", "rccl"), choices=["torch", "rccl"],
                     help="how the engine's collectives travel for N > 1: torch.distributed callbacks, or the native librccl transport (csrc/comm_rccl)")
-    ap.add_argument("--config4", type=int, default=-1, help="also time BASELINE config 4 (H2O-shaped, m = 1e7 sharded over the ranks): -1 = only when N == 8")
+    ap.add_argument("--config4", type=int, default=-1, help="with --full: also time BASELINE config 4 (H2O-shaped, m = 1e7 sharded over the ranks): -1 = only when N == 8")
     args = ap.parse_args()
 
     if args.gpus < 1:
         sys.stderr.write("bench.py: --gpus must be >= 1\n")
+        sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        sys.stderr.write("bench.py: --steps must be >= 1 and --warmup >= 0\n")
         sys.exit(2)
     # stdout carries ONE JSON line and nothing else: librccl prints a version banner to file descriptor 1 when a communicator
     # is created, so everything written to fd 1 from here on goes to stderr and the result line is written to the saved descriptor
@@ -399,7 +440,7 @@ def main():
 
     result = run_workload(args, args.shape, args.m, world, rank, device, dist, args.steps, args.warmup, primary=True)
     # BASELINE config 4 beside the headline: H2O-shaped, m = 1e7 hash-sharded over the ranks (default: only at N == 8)
-    want4 = args.config4 > 0 or (args.config4 < 0 and world == 8)
+    want4 = args.full and (args.config4 > 0 or (args.config4 < 0 and world == 8))
     if want4:
         r4 = run_workload(args, "H2O", int(os.environ.get("FRIES_BENCH_M4", "10000000")), world, rank, device, dist, max(5, args.steps // 2), min(args.warmup, 5), primary=False)
         if rank == 0:

@@ -421,7 +421,35 @@ def gen_tr(manifest):
             manifest["hbpiv_tr_runs"][name] = dict(run=run, n_iter=n_iter, spin_parity=parity, cases=[list(c) for c in cases])
 
 
+N2_LOAD_SAMPLE = 10000      # stored determinants kept per rank file
+
+
+def gen_n2_load_sample():
+    """tests/golden/n2_load_sample/: hash.dat as it is and, of every dets<rank>.dat of the reference's own 8-rank checkpoint N2_load/
+    that is a whole number of 7-byte indices, a fixed seeded sample of its used slots in file order (same 7-byte format)."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import golden_io
+    src = os.path.join(golden_io.reference_dir(), "N2_load")
+    dst = os.path.join(GOLD, "n2_load_sample")
+    os.makedirs(dst, exist_ok=True)
+    with open(os.path.join(src, "hash.dat"), "rb") as f, open(os.path.join(dst, "hash.dat"), "wb") as g:
+        g.write(f.read())
+    nb = 7
+    for r in range(1, 8):
+        raw = np.fromfile(os.path.join(src, f"dets{r}.dat"), dtype=np.uint8)
+        if raw.size % nb:
+            continue
+        rows = raw.reshape(-1, nb)
+        used = np.nonzero(rows.any(axis=1))[0]
+        pick = np.sort(np.random.default_rng(1000 + r).choice(used, size=N2_LOAD_SAMPLE, replace=False))
+        rows[pick].tofile(os.path.join(dst, f"dets{r}.dat"))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--only-n2-load-sample":
+        gen_n2_load_sample()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "--only-reload":
         with open(os.path.join(GOLD, "manifest.json")) as f:
             manifest = json.load(f)

@@ -7,6 +7,15 @@ import numpy as np
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+def reference_dir():
+    """Where oracle/Makefile looks for the reference's source tree (its REF variable; the environment overrides it as in make), or None."""
+    ref = os.environ.get("REF")
+    if not ref:
+        with open(os.path.join(os.path.dirname(GOLD), os.pardir, "oracle", "Makefile")) as f:
+            ref = next((ln.split("?=")[1].strip() for ln in f if ln.startswith("REF") and "?=" in ln), None)
+    return ref if ref and os.path.isdir(ref) else None
+
+
 def manifest():
     with open(os.path.join(GOLD, "manifest.json")) as f:
         return json.load(f)

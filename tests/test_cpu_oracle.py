@@ -537,20 +537,17 @@ def test_product_never_imports_oracle():
                 assert "oracle" not in txt.lower() or fn == "engine.py" and False, os.path.join(dirpath, fn)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/N2_load"), reason="the reference's own checkpoint dumps live only in the build container")
-def test_reference_checkpoint_dumps_shard_by_our_proc_hash():
-    """f-3: the checkpoint an 8-rank run of the REFERENCE left in N2_load/ (dets<rank>.dat: 7-byte indices of 26 orbitals; hash.dat: the
-    proc scrambler, raw uint32[52]).  Every index stored by rank r must hash to r under DistVec::idx_to_proc as restated here
-    (hash_fxn with the 32-bit-wrapped term, det_hash.hpp:160-170; % 8) for most of its entries (see below) and all of them carry
-    5 + 5 electrons.  Files that are whole multiples of 7 bytes only (two of the blobs are truncated)."""
+def _check_checkpoint_shards(d):
+    """-> number of stored determinants of the checkpoint directory d that were checked (see the test below)."""
     import oracle_lib
     lib = oracle_lib.load()
-    d = "/root/reference/N2_load/"
     scr = np.fromfile(d + "hash.dat", dtype=np.uint32)
     assert scr.size == 52
     n_orb, nb, P = 26, 7, 8
     checked = 0
     for r in range(1, 8):
+        if not os.path.exists(d + f"dets{r}.dat"):               # (the stored sample leaves the truncated files out)
+            continue
         raw = np.fromfile(d + f"dets{r}.dat", dtype=np.uint8)
         if raw.size % nb:
             continue
@@ -584,7 +581,20 @@ def test_reference_checkpoint_dumps_shard_by_our_proc_hash():
             occ = np.array([o for o in range(52) if (int(dets[i]) >> o) & 1], dtype=np.uint8)
             assert int(lib.fo_hash(occ.ctypes.data_as(ctypes.c_void_p), 10, scr.ctypes.data_as(ctypes.c_void_p))) == int(h[i])
         checked += dets.size
-    assert checked > 2_000_000
+    return checked
+
+
+def test_reference_checkpoint_dumps_shard_by_our_proc_hash():
+    """f-3: the checkpoint an 8-rank run of the REFERENCE left in N2_load/ (dets<rank>.dat: 7-byte indices of 26 orbitals; hash.dat: the
+    proc scrambler, raw uint32[52]).  Every index stored by rank r must hash to r under DistVec::idx_to_proc as restated here
+    (hash_fxn with the 32-bit-wrapped term, det_hash.hpp:160-170; % 8) for most of its entries (see below) and all of them carry
+    5 + 5 electrons.  Files that are whole multiples of 7 bytes only (two of the blobs are truncated).
+    tests/golden/n2_load_sample/ holds hash.dat and 10 000 used slots of each of the five whole files (oracle/gen_golden.py
+    --only-n2-load-sample: seeded choice, file order); where the reference's own directory is present, all of it is checked as well."""
+    assert _check_checkpoint_shards(os.path.join(golden_io.GOLD, "n2_load_sample") + "/") == 50_000
+    ref = golden_io.reference_dir()
+    if ref and os.path.isdir(os.path.join(ref, "N2_load")):
+        assert _check_checkpoint_shards(os.path.join(ref, "N2_load") + "/") > 2_000_000
 
 
 def test_legacy_hf_directory_reader_matches_reference(tmp_path):

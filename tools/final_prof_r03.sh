@@ -4,8 +4,8 @@ export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/final3
 mkdir -p $O
 step() { echo "$(date +%T) $*" >> $O/progress.txt; }
-step bench; timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-step bench_all; FRIES_BENCH_TOPK=80 timeout -k 10 200 python bench.py --cpu-iters 0 > $O/bench_all_kernels.json 2> /dev/null; echo "bench_all rc=$?"
+step bench; timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+step bench_all; FRIES_BENCH_TOPK=80 timeout -k 10 200 python bench.py --full --cpu-iters 0 > $O/bench_all_kernels.json 2> /dev/null; echo "bench_all rc=$?"
 step rocprof_stats; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 20 --warmup 5 --cpu-iters 0 > $O/prof_stdout.txt 2>&1; echo "prof rc=$?"
 f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/kernel_stats.csv
 f=$(find $O/prof -name "*kernel_trace.csv" | head -1); [ -n "$f" ] && python tools/gap_analysis.py $f > $O/gaps.txt
