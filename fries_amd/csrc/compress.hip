@@ -338,6 +338,7 @@ void fr_sys_comp(FriesCtx *c, uint32_t n_samp, double rn) {
     hipStream_t st = c->stream;
     uint32_t bound = c->h_vst.curr_size ? c->h_vst.curr_size : 1;
     uint32_t *kin = c->W.kin;      // HB-PP scratch is idle here
+    c->comp_pending = false;       // the deletes release positions: a matrix-compression result left on the device is stale from here on
     AccUnkept au{c->vec.v0, B.keep, c->vec.st};
     run_seq(c, B.seq, au, bound);
     const int P = c->n_ranks;

@@ -212,6 +212,8 @@ struct FriesCtx {
     bool warm_start = true;
     uint32_t *c_pos = nullptr, *c_orbs = nullptr; double *c_val = nullptr;   // compacted apply_HBPP_sys output
     uint32_t *d_nsucc = nullptr;
+    bool comp_pending = false;               // c_pos / c_orbs / c_val hold the result of fries_apply_hbpp_sys / _piv on the vector as it stands (fries_spawn_from_comp);
+                                             // whatever moves positions -- a merge, a vector compression, a load, the setup -- clears it
     SpawnBuf sp{};
     VcompBuf vc{};
     PivBuf piv{};

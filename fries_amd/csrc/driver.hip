@@ -142,7 +142,7 @@ static void frisys_setup(FriesCtx *c, const fries_frisys_params *p) {
     if (!c->d_eris) throw FriesError("fries_set_molecule must be called first");
     c->eps = p->epsilon; c->target_norm = p->target_norm; c->init_thresh = p->initiator;
     c->vec_nonz = p->vec_nonz; c->mat_nonz = p->mat_nonz; c->new_hb = p->hb_unnorm != 0;
-    c->en_shift = 0; c->last_one_norm = 0; c->iterat = 0;
+    c->en_shift = 0; c->last_one_norm = 0; c->iterat = 0; c->comp_pending = false;
     if (p->max_dets == 0 || p->mat_nonz == 0 || p->vec_nonz == 0) throw FriesError("max_dets, mat_nonz and vec_nonz must be positive");
     c->mt.seed(p->seed);
     c->proc_scr.resize(2 * c->n_orb); c->vec_scr.resize(2 * c->n_orb);
@@ -241,8 +241,51 @@ static __global__ void k_dense_norm(VecDev V, double *out) {
     *out = r;
 }
 
-static void frisys_iterate(FriesCtx *c, fries_iter_log *lg) {
+// The three pieces of the iteration that fries_frisys_iterate and the stepwise entry points (fries_spawn_from_comp, fries_dense_apply,
+// fries_dense_norm) share: each enqueues one fixed sequence, whoever calls it.
+// Spawning + annihilation (:429-471) from the compression result in c_pos / c_orbs / c_val / d_nsucc; -> an upper bound of the positions taken.
+static uint32_t fr_spawn_comp_result(FriesCtx *c, double eps, double init_thresh) {
+    if (c->num_success > c->sp.cap) throw FriesError("spawn buffer too small");
+    if (c->num_success) FR_LAUNCH(c, "k_spawn_build", k_spawn_build, dim3(fr_blocks(c->num_success, FR_BLOCK)), dim3(FR_BLOCK), c->vec, c->sp, c->c_pos, c->c_orbs, c->c_val, c->d_nsucc, eps, init_thresh);
+    uint32_t n_merge = c->num_success;
+    bool merged = false;            // the Adder filled up: the passes went through several perform_add rounds, each merged on arrival
+    if (c->use_comm) n_merge = fr_spawn_exchange(c, c->num_success, 0, &merged);      // every rank takes part, also with nothing to send
+    if (n_merge && !merged) fr_vec_merge(c, &c->vec, n_merge, false);
+    return n_merge;
+}
+// The dense block of H applied exactly (:480-485): value at the origin x stored element, added as initiator contributions in the stored
+// order, as a perform_add of its own (with ranks: an exchange of its own, every rank taking part); -> an upper bound of the positions taken.
+static uint32_t fr_dense_multiply(FriesCtx *c) {
+    if (!c->n_dense_h_glob) return 0;
+    uint32_t m = 0;
+    if (c->n_dense_h_nz) {
+        FR_LAUNCH(c, "k_dense_spawn", k_dense_spawn, dim3(1), dim3(FR_BLOCK), c->vec, c->sp, c->d_dh_from, c->d_dh_to, c->d_dh_el, c->n_dense_h_nz);
+        FR_HIP(hipMemcpyAsync(&m, c->sp.n_spawn, 4, hipMemcpyDeviceToHost, c->stream));
+        FR_HIP(hipStreamSynchronize(c->stream));
+    }
+    const uint32_t n_merge_dense = c->use_comm ? fr_spawn_exchange(c, m) : m;      // all of them carry the initiator flag: one pass in effect
+    if (n_merge_dense) fr_vec_merge(c, &c->vec, n_merge_dense, false);
+    return n_merge_dense;
+}
+// sol_vec.dense_norm() (:503, vec_utils.hpp:903-918: sum_mpi of the ranks' sums); 0 without a dense space
+static double fr_dense_norm_all(FriesCtx *c) {
+    if (!(c->n_dense_h_glob || c->vec.n_dense)) return 0;
     hipStream_t st = c->stream;
+    FR_LAUNCH(c, "k_dense_norm", k_dense_norm, dim3(1), dim3(1), c->vec, c->d_dense_norm);
+    const double *src = c->d_dense_norm;
+    if (c->use_comm) {
+        FR_HIP(hipMemcpyAsync(c->comm.small_send, c->d_dense_norm, 8, hipMemcpyDeviceToDevice, st));
+        src = (const double *)fr_allgather(c, 8);
+    }
+    double h[FR_MAX_RANKS];
+    FR_HIP(hipMemcpyAsync(h, src, 8 * (size_t)c->n_ranks, hipMemcpyDeviceToHost, st));
+    FR_HIP(hipStreamSynchronize(st));
+    double dn = 0;
+    for (int p = 0; p < c->n_ranks; p++) dn += h[p];
+    return dn;
+}
+
+static void frisys_iterate(FriesCtx *c, fries_iter_log *lg) {
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     fr_vec_maybe_rebuild(c, &c->vec);
     // systematic matrix compression (:414-422)
@@ -250,26 +293,9 @@ static void frisys_iterate(FriesCtx *c, fries_iter_log *lg) {
     for (int k = 0; k < 5; k++) rn[k] = uni(c->mt);
     fr_hbpp_apply(c, c->mat_nonz - c->n_dense_h_glob, rn);      // :421 matr_samp - tot_dense_h
     uint32_t vec_size = c->h_vst.curr_size;
-    // spawning + annihilation (:429-471)
-    if (c->num_success > c->sp.cap) throw FriesError("spawn buffer too small");
-    if (c->num_success) FR_LAUNCH(c, "k_spawn_build", k_spawn_build, dim3(fr_blocks(c->num_success, FR_BLOCK)), dim3(FR_BLOCK), c->vec, c->sp, c->c_pos, c->c_orbs, c->c_val, c->d_nsucc, c->eps, c->init_thresh);
-    uint32_t n_merge = c->num_success;
-    bool merged = false;            // the Adder filled up: the passes went through several perform_add rounds, each merged on arrival
-    if (c->use_comm) n_merge = fr_spawn_exchange(c, c->num_success, 0, &merged);      // every rank takes part, also with nothing to send
-    if (n_merge && !merged) fr_vec_merge(c, &c->vec, n_merge, false);
-    uint32_t n_merge_dense = 0;
-    if (c->n_dense_h_glob) {
-        // the dense block of H applied exactly (:480-485): value at the origin x stored element, added as initiator contributions in
-        // the stored order, as a perform_add of its own (with ranks: an exchange of its own, every rank taking part)
-        uint32_t m = 0;
-        if (c->n_dense_h_nz) {
-            FR_LAUNCH(c, "k_dense_spawn", k_dense_spawn, dim3(1), dim3(FR_BLOCK), c->vec, c->sp, c->d_dh_from, c->d_dh_to, c->d_dh_el, c->n_dense_h_nz);
-            FR_HIP(hipMemcpyAsync(&m, c->sp.n_spawn, 4, hipMemcpyDeviceToHost, st));
-            FR_HIP(hipStreamSynchronize(st));
-        }
-        n_merge_dense = c->use_comm ? fr_spawn_exchange(c, m) : m;      // all of them carry the initiator flag: one pass in effect
-        if (n_merge_dense) fr_vec_merge(c, &c->vec, n_merge_dense, false);
-    }
+    // spawning + annihilation (:429-471), then the dense block (:480-485)
+    const uint32_t n_merge = fr_spawn_comp_result(c, c->eps, c->init_thresh);
+    const uint32_t n_merge_dense = fr_dense_multiply(c);
     // no host look at the vector's state here: the kernels read the stored size themselves, the launches only need an upper bound of it
     // (every merged spawn may have taken a new position); an overflow raised by the merge is reported at the end of the iteration
     {
@@ -286,20 +312,7 @@ static void frisys_iterate(FriesCtx *c, fries_iter_log *lg) {
     double glob_norm = 0;
     fr_find_preserve(c, &n_samp, &glob_norm);
     fr_dots_collect(c, h_dots, &c->numer, &c->denom);
-    if (c->n_dense_h_glob || c->vec.n_dense) {       // glob_norm += sol_vec.dense_norm() (:503, vec_utils.hpp:903-918: sum_mpi of the ranks' sums)
-        FR_LAUNCH(c, "k_dense_norm", k_dense_norm, dim3(1), dim3(1), c->vec, c->d_dense_norm);
-        const double *src = c->d_dense_norm;
-        if (c->use_comm) {
-            FR_HIP(hipMemcpyAsync(c->comm.small_send, c->d_dense_norm, 8, hipMemcpyDeviceToDevice, st));
-            src = (const double *)fr_allgather(c, 8);
-        }
-        double h[FR_MAX_RANKS];
-        FR_HIP(hipMemcpyAsync(h, src, 8 * (size_t)c->n_ranks, hipMemcpyDeviceToHost, st));
-        FR_HIP(hipStreamSynchronize(st));
-        double dn = 0;
-        for (int p = 0; p < c->n_ranks; p++) dn += h[p];
-        glob_norm += dn;
-    }
+    if (c->n_dense_h_glob || c->vec.n_dense) glob_norm += fr_dense_norm_all(c);       // glob_norm += sol_vec.dense_norm() (:503)
     c->glob_norm = glob_norm;
     c->nkept = c->vec_nonz - n_samp;
     const unsigned shift_interval = 10;
@@ -1092,6 +1105,7 @@ extern "C" int fries_vec_load(fries_ctx *h, const uint64_t *dets, const double *
     FR_HIP(hipSetDevice(c->device));
     VecDev &v = c->vec;
     if (n > v.cap) throw FriesError("vector larger than max_dets");
+    c->comp_pending = false;
     FR_HIP(hipMemsetAsync(v.v0, 0, 8 * (size_t)v.cap, c->stream));
     FR_HIP(hipMemsetAsync(v.v1, 0, 8 * (size_t)v.cap, c->stream));
     FR_HIP(hipMemsetAsync(v.diag, 0xff, 8 * (size_t)v.cap, c->stream));
@@ -1135,12 +1149,14 @@ extern "C" int fries_apply_hbpp_sys(fries_ctx *h, uint32_t n_samp, const double 
     FR_API_BEGIN
     FriesCtx *c = &h->c;
     FR_HIP(hipSetDevice(c->device));
+    c->comp_pending = false;
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     if (unit_matrel) fr_hbpp_apply_unit(c, n_samp, rn); else fr_hbpp_apply(c, n_samp, rn);
     size_t m = c->num_success;
     if (n_out) *n_out = m;
     if (comp_len) for (int k = 0; k < 5; k++) comp_len[k] = c->comp_len[k];
     check_dev_err(c);
+    c->comp_pending = true;     // the result stays in c_pos / c_orbs / c_val / d_nsucc for fries_spawn_from_comp and fries_comp_download
     if (cap < m) throw FriesError("output buffer too small");
     if (det_pos) FR_HIP(hipMemcpy(det_pos, c->c_pos, 4 * m, hipMemcpyDeviceToHost));
     if (orbs) FR_HIP(hipMemcpy(orbs, c->c_orbs, 4 * m, hipMemcpyDeviceToHost));
@@ -1156,12 +1172,76 @@ extern "C" int fries_apply_hbpp_piv(fries_ctx *h, uint32_t n_samp, int unit_matr
     if (c->hh_mode || c->fq_mode || !c->W.cap) throw FriesError("fries_apply_hbpp_piv needs a context set up by fries_frisys_setup");
     if (c->spin_parity && !c->new_hb) throw FriesError("Time-reversal symmetry is only implemented for the unnormalized heat-bath distribution");       // heat_bathPP.cpp:1019-1021
     uint32_t sl[5] = {0, 0, 0, 0, 0};
+    c->comp_pending = false;
     fr_hbpp_piv_apply(c, n_samp, unit_matrel, sl);
     size_t m = c->num_success;
     if (n_out) *n_out = m;
     if (stage_len) for (int k = 0; k < 5; k++) stage_len[k] = sl[k];
     check_dev_err(c);
+    c->comp_pending = true;
     if (cap < m) throw FriesError("output buffer too small");
+    if (det_pos) FR_HIP(hipMemcpy(det_pos, c->c_pos, 4 * m, hipMemcpyDeviceToHost));
+    if (orbs) FR_HIP(hipMemcpy(orbs, c->c_orbs, 4 * m, hipMemcpyDeviceToHost));
+    if (vals) FR_HIP(hipMemcpy(vals, c->c_val, 8 * m, hipMemcpyDeviceToHost));
+    FR_API_END
+}
+
+// ---- the loop body between apply_HBPP_sys and death / cloning (frisys_mol.cpp:424-485) for a host that keeps its own loop
+static void need_frisys(FriesCtx *c, const char *who) {
+    if (c->hh_mode || c->fq_mode || c->full_mode || !c->W.cap) throw FriesError(std::string(who) + " needs a context set up by fries_frisys_setup");
+}
+// frisys_mol.cpp:429-471 on the result the last fries_apply_hbpp_sys / fries_apply_hbpp_piv left on the device
+extern "C" int fries_spawn_from_comp(fries_ctx *h, double eps, double init_thresh) {
+    FR_API_BEGIN
+    FriesCtx *c = &h->c;
+    need_frisys(c, "fries_spawn_from_comp");
+    if (!c->comp_pending) throw FriesError("fries_spawn_from_comp: no compression result is pending -- call fries_apply_hbpp_sys or fries_apply_hbpp_piv first "
+                                           "(a merge, a vector compression, fries_vec_load and fries_spawn_from_comp itself discard the result: its positions are those of the vector as it stood)");
+    c->comp_pending = false;
+    FR_HIP(hipSetDevice(c->device));
+    fr_vec_sync_state(c, &c->vec, &c->h_vst);
+    fr_vec_maybe_rebuild(c, &c->vec);           // tombstones of earlier deletes (the fused loop does this once per iteration)
+    fr_spawn_comp_result(c, eps, init_thresh);
+    check_dev_err(c);
+    FR_API_END
+}
+// frisys_mol.cpp:480-485
+extern "C" int fries_dense_apply(fries_ctx *h) {
+    FR_API_BEGIN
+    FriesCtx *c = &h->c;
+    need_frisys(c, "fries_dense_apply");
+    if (!c->n_dense_h_glob) return 0;
+    FR_HIP(hipSetDevice(c->device));
+    fr_dense_multiply(c);
+    check_dev_err(c);
+    FR_API_END
+}
+// sol_vec.dense_norm() of frisys_mol.cpp:504
+extern "C" int fries_dense_norm(fries_ctx *h, double *norm) {
+    FR_API_BEGIN
+    FriesCtx *c = &h->c;
+    need_frisys(c, "fries_dense_norm");
+    FR_HIP(hipSetDevice(c->device));
+    const double dn = fr_dense_norm_all(c);
+    if (norm) *norm = dn;
+    FR_API_END
+}
+extern "C" int fries_dense_h_count(fries_ctx *h, uint32_t *global_count) {
+    FR_API_BEGIN
+    need_frisys(&h->c, "fries_dense_h_count");
+    if (global_count) *global_count = h->c.n_dense_h_glob;
+    FR_API_END
+}
+extern "C" int fries_comp_download(fries_ctx *h, uint32_t *det_pos, uint8_t *orbs, double *vals, size_t cap, size_t *n_out) {
+    FR_API_BEGIN
+    FriesCtx *c = &h->c;
+    need_frisys(c, "fries_comp_download");
+    if (!c->comp_pending) throw FriesError("fries_comp_download: no compression result is pending");
+    FR_HIP(hipSetDevice(c->device));
+    const size_t m = c->num_success;
+    if (n_out) *n_out = m;
+    if (cap < m) throw FriesError("output buffer too small");
+    FR_HIP(hipStreamSynchronize(c->stream));
     if (det_pos) FR_HIP(hipMemcpy(det_pos, c->c_pos, 4 * m, hipMemcpyDeviceToHost));
     if (orbs) FR_HIP(hipMemcpy(orbs, c->c_orbs, 4 * m, hipMemcpyDeviceToHost));
     if (vals) FR_HIP(hipMemcpy(vals, c->c_val, 8 * m, hipMemcpyDeviceToHost));

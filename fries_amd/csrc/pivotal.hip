@@ -496,6 +496,7 @@ static uint32_t piv_budget(FriesCtx *c, const std::vector<double> &norms, uint32
 static void piv_comp_core(FriesCtx *c, uint32_t compress_size, uint32_t *n_kept, double *glob_norm_out, bool flat) {
     VcompBuf &B = c->vc;
     hipStream_t st = c->stream;
+    if (!flat) c->comp_pending = false;      // the solution vector's deletes release positions (fries_spawn_from_comp's guard)
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     const uint32_t bound = c->h_vst.curr_size ? c->h_vst.curr_size : 1;
     const uint32_t save = c->vec_nonz;

@@ -488,6 +488,7 @@ void fr_vec_merge(FriesCtx *c, VecDev *v, uint32_t n_bound, bool same_column, bo
     SpawnBuf &S = c->sp;
     hipStream_t st = c->stream;
     if (n_bound > S.cap) throw FriesError("spawn list exceeds spawn buffer capacity");
+    c->comp_pending = false;        // new positions, re-used holes: a compression result left on the device no longer describes this vector
     fr_vec_reserve_hash(c, v, n_bound);
     v->used_ub = (uint32_t)((uint64_t)v->used_ub + n_bound < 0xFFFFFFFFull ? v->used_ub + n_bound : 0xFFFFFFFFu);
     unsigned g1 = fr_blocks(n_bound, FR_BLOCK), gt = fr_blocks(n_bound, FR_TILE);

@@ -27,6 +27,7 @@ EXPORTS = [
     "fries_rccl_unique_id", "fries_rccl_create", "fries_local_group_create", "fries_local_group_destroy", "fries_local_create", "fries_transport_comm", "fries_transport_counts", "fries_transport_destroy",
     "fries_set_proc_scrambler", "fries_tie_margins", "fries_measure_copy_bandwidth", "fries_piv_stats", "fries_set_trial_vector", "fries_set_initial_vector", "fries_set_ham_shift", "fries_vec_add_to", "fries_death_clone", "fries_dots", "fries_find_preserve", "fries_sys_comp",
     "fries_vec_column_download", "fries_vec_column_upload", "fries_vec_column_zero", "fries_vec_diag_download", "fries_vec_dot_list", "fries_vec_add_vecs", "fries_set_det_space", "fries_vec_set_dense", "fries_dense_sizes", "fries_hostcomm_create", "fries_set_vec_scrambler", "fries_hh_comp_sub", "fries_hh_ref_ovlp", "fries_set_spin_parity", "fries_h_offdiag_list",
+    "fries_spawn_from_comp", "fries_dense_apply", "fries_dense_norm", "fries_dense_h_count", "fries_comp_download",
 ]
 
 
@@ -158,6 +159,17 @@ def load_library() -> C.CDLL:
     lib.fries_stream.restype = C.c_void_p
     lib.fries_stream.argtypes = [C.c_void_p]
     lib.fries_idx_to_proc.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.fries_vec_add_to.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.fries_death_clone.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_uint32]
+    lib.fries_dots.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.fries_find_preserve.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+    lib.fries_sys_comp.argtypes = [C.c_void_p, C.c_uint32, C.c_double]
+    lib.fries_dense_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.fries_spawn_from_comp.argtypes = [C.c_void_p, C.c_double, C.c_double]
+    lib.fries_dense_apply.argtypes = [C.c_void_p]
+    lib.fries_dense_norm.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.fries_dense_h_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.fries_comp_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     _lib = lib
     return lib
 
@@ -258,6 +270,9 @@ class FriEngine:
         p = FrisysParams(epsilon, target_norm, initiator, vec_nonz, mat_nonz, max_dets, seed, 1 if distribution == "HB_unnorm" else 0)
         self._ck(self.lib.fries_frisys_setup(self.h, C.byref(p)))
         self.max_dets = max_dets
+        # what iterate_stepwise needs of the run: the parameters, and the driver's own loop state (frisys_mol.cpp:112-113, 405)
+        self._step = dict(eps=float(epsilon), init_thresh=float(initiator), target_norm=float(target_norm), vec_nonz=int(vec_nonz), mat_nonz=int(mat_nonz),
+                          shift=0.0, last_one_norm=0.0, iterat=0, dense=None)
 
     # ---- fciqmc_mol
     def setup_fciqmc(self, *, epsilon, target_walkers, max_dets, initiator=0, seed=0, distribution="NU", trial=None, ini=None, fp=False):
@@ -333,6 +348,121 @@ class FriEngine:
         logs = np.zeros(n_iter, dtype=ITERLOG_DTYPE) if want_logs else None
         assert ITERLOG_DTYPE.itemsize == C.sizeof(IterLog)
         self._ck(self.lib.fries_frisys_iterate(self.h, n_iter, _ptr(logs) if want_logs else None))
+        return logs
+
+    # ---- frisys_mol step by step: the operators of one iteration as single calls (nothing but scalars crosses PCIe)
+    def apply_hbpp_sys_device(self, n_samp: int, rn):
+        """apply_HBPP_sys with the result left on the device (for spawn_from_comp / comp_download); returns (num_success, comp_len[5])."""
+        rn = np.ascontiguousarray(rn, dtype=np.float64)
+        m = C.c_size_t()
+        cl = np.zeros(5, dtype=np.uint32)
+        self._ck(self.lib.fries_apply_hbpp_sys(self.h, n_samp, _ptr(rn), 0, None, None, None, C.c_size_t(-1).value, C.byref(m), _ptr(cl)))
+        return m.value, cl
+
+    def spawn_from_comp(self, eps: float, init_thresh: float):
+        """frisys_mol.cpp:429-471 on the compression result pending on the device; raises when none is pending."""
+        self._ck(self.lib.fries_spawn_from_comp(self.h, eps, init_thresh))
+
+    def dense_apply(self):
+        """frisys_mol.cpp:480-485: the dense block of H times column 0 into column 1 (no-op without a dense space)."""
+        self._ck(self.lib.fries_dense_apply(self.h))
+
+    def dense_norm(self) -> float:
+        out = C.c_double()
+        self._ck(self.lib.fries_dense_norm(self.h, C.byref(out)))
+        return out.value
+
+    def dense_h_count(self) -> int:
+        """tot_dense_h: matrix elements inside the dense space over all ranks."""
+        out = C.c_uint32()
+        self._ck(self.lib.fries_dense_h_count(self.h, C.byref(out)))
+        return out.value
+
+    def dense_sizes(self):
+        """Every rank's dense-space size (dense.txt)."""
+        out = np.zeros(64, dtype=np.uint32)
+        n = C.c_size_t()
+        self._ck(self.lib.fries_dense_sizes(self.h, _ptr(out), out.size, C.byref(n)))
+        return out[:n.value].copy()
+
+    def comp_download(self, cap: int = None):
+        """The compression result pending on the device: (positions, orbitals, values)."""
+        m = C.c_size_t()
+        if cap is None:
+            if self.lib.fries_comp_download(self.h, None, None, None, 0, C.byref(m)) != 0 and m.value == 0:
+                raise RuntimeError(self.lib.fries_last_error().decode())
+            cap = m.value
+        pos = np.zeros(max(cap, 1), dtype=np.uint32)
+        orbs = np.zeros((max(cap, 1), 4), dtype=np.uint8)
+        vals = np.zeros(max(cap, 1))
+        self._ck(self.lib.fries_comp_download(self.h, _ptr(pos), _ptr(orbs), _ptr(vals), cap, C.byref(m)))
+        k = m.value
+        return pos[:k].copy(), orbs[:k].copy(), vals[:k].copy()
+
+    def vec_add_to(self, column: int, dets, vals, ini):
+        """DistVec::add x n + perform_add into `column` (what this rank received, in arrival order)."""
+        d = np.ascontiguousarray(dets, dtype=np.uint64)
+        v = np.ascontiguousarray(vals, dtype=np.float64)
+        f = np.ascontiguousarray(ini, dtype=np.uint8)
+        self._ck(self.lib.fries_vec_add_to(self.h, column, _ptr(d), _ptr(v), _ptr(f), d.size))
+
+    def death_clone(self, eps: float, shift: float, vec_size: int):
+        """frisys_mol.cpp:487-499."""
+        self._ck(self.lib.fries_death_clone(self.h, eps, shift, vec_size))
+
+    def dots(self):
+        """(numerator, denominator) of the projected energy (frisys_mol.cpp:511-517)."""
+        a, b = C.c_double(), C.c_double()
+        self._ck(self.lib.fries_dots(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def find_preserve(self, n_samp: int):
+        """find_preserve on column 0 with budget n_samp; returns (samples left, one-norm before compression)."""
+        ns = C.c_uint32(n_samp)
+        gn = C.c_double()
+        self._ck(self.lib.fries_find_preserve(self.h, C.byref(ns), C.byref(gn)))
+        return ns.value, gn.value
+
+    def sys_comp(self, n_samp: int, rn: float):
+        """sys_comp after find_preserve, with the driver's deletes."""
+        self._ck(self.lib.fries_sys_comp(self.h, n_samp, rn))
+
+    def iterate_stepwise(self, n_iter: int):
+        """frisys_mol.cpp:405-552 written out over the single-operator calls -- the loop a host that keeps its own driver would write.
+        Same log fields as iterate().  The shift, the last one-norm and the iteration count of this loop are kept here, as the
+        reference's driver keeps them in its own variables: continue a run with the loop it was started with."""
+        import math
+        st = self._step
+        eps, shift_interval, shift_damping = st["eps"], 10, 0.05
+        if st["dense"] is None:
+            st["dense_h"] = self.dense_h_count()
+            st["dense"] = bool(st["dense_h"]) or bool(self.dense_sizes().any())
+        logs = np.zeros(n_iter, dtype=ITERLOG_DTYPE)
+        for k in range(n_iter):
+            rn = [self.next_draw() / 2.0 ** 32 for _ in range(5)]
+            num_success, comp_len = self.apply_hbpp_sys_device(st["mat_nonz"] - st["dense_h"], rn)       # :414-422
+            vec_size = self.vec_info()[0]
+            self.spawn_from_comp(eps, st["init_thresh"])                                                # :429-471
+            self.dense_apply()                                                                          # :480-485
+            self.death_clone(eps, st["shift"], vec_size)                                                # :487-499
+            numer, denom = self.dots()                                                                  # :511-517
+            n_samp, glob_norm = self.find_preserve(st["vec_nonz"])                                      # :503
+            if st["dense"]:
+                glob_norm += self.dense_norm()                                                          # :504
+            if (st["iterat"] + 1) % shift_interval == 0:                                                # adjust_shift, compress_utils.cpp:684-693
+                damp = shift_damping / shift_interval / eps
+                if st["last_one_norm"]:
+                    st["shift"] -= damp * math.log(glob_norm / st["last_one_norm"])
+                    st["last_one_norm"] = glob_norm
+                if st["last_one_norm"] == 0 and glob_norm > st["target_norm"]:
+                    st["last_one_norm"] = glob_norm
+            self.sys_comp(n_samp, self.next_draw() / 2.0 ** 32)                                         # :526-539
+            st["iterat"] += 1
+            curr_size, n_nonz, _ = self.vec_info()
+            lg = logs[k]
+            lg["numer"], lg["denom"], lg["shift"], lg["norm"] = numer, denom, st["shift"], glob_norm
+            lg["nkept"], lg["n_nonz"], lg["curr_size"], lg["num_success"] = st["vec_nonz"] - n_samp, n_nonz, curr_size, num_success
+            lg["comp_len"] = comp_len
         return logs
 
     def vec_info(self):

@@ -322,6 +322,12 @@ inline void apply_HBPP_sys(Matrix<uint8_t> & /*all_orbs*/, Matrix<uint8_t> &all_
     v->before_device_op();
     size_t n_out = 0;
     uint32_t stage_len[5];
+    if (fries_hip::Backend::get().comp_on_device) {
+        // FRIES/device_loop.hpp: the result stays on the device for fries_hip::spawn_from_comp; fries_hip::comp_download fetches the arrays when asked
+        fries_hip::ck(fries_apply_hbpp_sys(v->ctx(), n_samp, rn, 0, nullptr, nullptr, nullptr, spawn_length, &n_out, stage_len));
+        comp_scratch->vec_len = n_out;
+        return;
+    }
     fries_hip::ck(fries_apply_hbpp_sys(v->ctx(), n_samp, rn, 0, comp_scratch->pos32.data(), (uint8_t *)comp_scratch->orb_indices1, comp_scratch->vec1.data(), spawn_length, &n_out, stage_len));
     for (size_t i = 0; i < n_out; i++) comp_scratch->det_indices2[i] = comp_scratch->pos32[i];
     comp_scratch->vec_len = n_out;

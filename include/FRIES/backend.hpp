@@ -97,6 +97,8 @@ struct Backend {
     /* bulk traffic of the mirrors over PCIe, per direction (FRIES_FACADE_STATS=1 prints the totals when the program ends) */
     uint64_t bytes_to_device = 0, bytes_to_host = 0, device_ops = 0;
     bool hh_mode = false;                                   // parse_hh_input ran: the context runs the Hubbard-Holstein model
+    bool comp_on_device = false;                            // FRIES/device_loop.hpp: apply_HBPP_sys leaves its result on the device and fills vec_len only
+    double loop_eps = 0;                                    // FRIES/device_loop.hpp (move_to_device): the time step the device tabulates the dense block of H with
     DeviceVecBase *owner_of(const void *p) { for (auto *v : vecs) if (v->owns(p)) return v; return nullptr; }
     DeviceVecBase *by_indices(const void *key) { for (auto *v : vecs) if (v->indices_key() == key) return v; return nullptr; }
     DeviceVecBase *bound_vec() { for (auto *v : vecs) if (v->bound()) return v; return nullptr; }

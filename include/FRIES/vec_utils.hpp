@@ -129,6 +129,7 @@ protected:
         }
         fries_frisys_params p{};
         p.max_dets = (uint32_t)max_size_; p.vec_nonz = (uint32_t)max_size_; p.mat_nonz = mat_nonz; p.hb_unnorm = new_hb ? 1 : 0;
+        p.epsilon = B.loop_eps;             // 0 unless FRIES/device_loop.hpp's move_to_device named it: only fries_dense_apply's table of H depends on it
         fries_hip::ck(fries_frisys_setup(cx, &p));
     }
     uint64_t word_at(size_t pos) const { return fries_word_of(indices_[pos], (uint8_t)indices_.cols()); }
@@ -349,6 +350,11 @@ public:
         if (bound_) { self->pull_col(col_); self->col_dirty_[col_] = true; }
         return (el_type *)vals_[col_];
     }
+    /*! (MI355X build, FRIES/device_loop.hpp) the address find_preserve / sys_comp recognise this vector by -- column 0 behind the dense
+     * space -- without refreshing the host mirror or marking it written; not to be read or written through while the vector is bound */
+    el_type *device_key() const { return (el_type *)vals_[0] + n_dense_; }
+    /*! (MI355X build, FRIES/device_loop.hpp) the indices() matrix as the name apply_HBPP_sys recognises this vector by, without refreshing it */
+    Matrix<uint8_t> &device_indices_key() { return indices_; }
     uint8_t num_vecs() const { return (uint8_t)vals_.rows(); }
     Matrix<uint8_t> &indices() { pull_idx(); return indices_; }
     size_t curr_size() const { const_cast<DistVec *>(this)->pull_info(); return curr_size_; }

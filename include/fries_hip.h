@@ -296,7 +296,8 @@ int fries_h_offdiag_list(fries_ctx *ctx, const uint64_t *dets, const double *val
 /* The hot-path operators one by one, on the context's solution vector. */
 /* apply_HBPP_sys (heat_bathPP.cpp:686-992) with the five uniforms it would draw; outputs as
  * comp_vecs.{det_indices2, orb_indices1, vec1}.  unit_matrel != 0 uses the |value| = 1 lambdas of
- * tests/test_hamiltonian.cpp:493-500. */
+ * tests/test_hamiltonian.cpp:493-500.  det_pos / orbs / vals may each be NULL: the result then stays on the device only
+ * (where fries_spawn_from_comp consumes it and fries_comp_download fetches it later); cap must still be >= *n_out. */
 int fries_apply_hbpp_sys(fries_ctx *ctx, uint32_t n_samp, const double rn[5], int unit_matrel,
                          uint32_t *det_pos, uint8_t *orbs, double *vals, size_t cap, size_t *n_out, uint32_t comp_len[5]);
 /* apply_HBPP_piv (heat_bathPP.cpp:1014-1419; spin_parity = what fries_set_spin_parity set): every factor multiplied out into the long vector, compressed by
@@ -305,6 +306,33 @@ int fries_apply_hbpp_sys(fries_ctx *ctx, uint32_t n_samp, const double rn[5], in
  * depends on the data.  stage_len[k] = elements after the k-th compression.  One factor may expand to at most 134e6 values. */
 int fries_apply_hbpp_piv(fries_ctx *ctx, uint32_t n_samp, int unit_matrel,
                          uint32_t *det_pos, uint8_t *orbs, double *vals, size_t cap, size_t *n_out, uint32_t stage_len[5]);
+/* ---- one FRI iteration of frisys_mol step by step, for a host that keeps its own loop: fries_apply_hbpp_sys (no download), the
+ * calls below, fries_death_clone, fries_dots, fries_find_preserve, fries_sys_comp.  Nothing larger than a few scalars crosses PCIe.
+ *
+ * fries_spawn_from_comp: frisys_mol.cpp:429-471.  Consumes the result the last fries_apply_hbpp_sys or fries_apply_hbpp_piv of this
+ * context left on the device: forms the spawns -eps * value * sign(origin) on the excited determinants (doub_det / sing_det) and adds
+ * them into column 1 in the reference's order -- non-initiator origins first, then initiators, |origin| >= init_thresh judged against
+ * column 0 -- as the two add passes + perform_add do.  With a communicator it is a collective: the exchange and the Adder rounds of
+ * fries_frisys_iterate (FRIES_ADDER_SIZE included); every rank enters it, also with nothing to send.  Column 1 must be zero on entry
+ * (as after setup and after fries_death_clone).  eps and init_thresh are the arguments, not the setup parameters.
+ * A compression result refers to positions of the vector as it stood: the context records that one is pending, and whatever changes the
+ * layout -- a merge (fries_vec_add*, this call), fries_sys_comp, fries_compress_vec*, fries_vec_load, the setup -- clears the record.
+ * With nothing pending the call returns -1 with a message and launches nothing. */
+int fries_spawn_from_comp(fries_ctx *ctx, double eps, double init_thresh);
+/* frisys_mol.cpp:480-485: the tabulated dense block of H (times -epsilon of fries_frisys_setup, as :347-397 tabulate it) times column 0,
+ * added into column 1 as a perform_add of its own.  Collective
+ * whenever the dense space is non-empty on any rank; returns 0 at once when there is no dense space. */
+int fries_dense_apply(fries_ctx *ctx);
+/* sol_vec.dense_norm() of frisys_mol.cpp:504 (vec_utils.hpp:903-918): summed in position order on the device, then over the ranks in
+ * rank order (collective with a dense space); 0 without one. */
+int fries_dense_norm(fries_ctx *ctx, double *norm);
+/* tot_dense_h (frisys_mol.cpp:399): the matrix elements inside the dense space over all ranks; the sample budget of :421 is
+ * mat_nonz - tot_dense_h. */
+int fries_dense_h_count(fries_ctx *ctx, uint32_t *global_count);
+/* the pending compression result, fetched after the fact (comp_vecs.{det_indices2, orb_indices1, vec1} of heat_bathPP.cpp:686-992);
+ * any pointer may be NULL; -1 when nothing is pending.  Does not consume the result. */
+int fries_comp_download(fries_ctx *ctx, uint32_t *det_pos, uint8_t *orbs, double *vals, size_t cap, size_t *n_out);
+
 /* find_preserve + sys_comp on column 0 (compress_utils.cpp:29-105, 283-327) followed by the deletes
  * of frisys_mol.cpp:534-539 */
 int fries_compress_vec(fries_ctx *ctx, uint32_t n_samp, double rn, uint32_t *n_kept, double *glob_norm);
