@@ -20,6 +20,7 @@ struct fries_transport {
     int kind = 0;               // 1 RCCL, 2 local
     int rank = 0, size = 1, device = 0;
     uint64_t big_bytes = 0;
+    DevMem mem;                 // owns the staging buffers below
     void *small_send = nullptr, *small_recv = nullptr, *big_send = nullptr, *big_recv = nullptr;
     uint64_t n_allgather = 0, n_alltoallv = 0;
     // RCCL
@@ -55,10 +56,10 @@ struct fries_local_group {
 
 static void tr_alloc(fries_transport *t) {
     FR_HIP(hipSetDevice(t->device));
-    t->small_send = fr_alloc<uint8_t>(FRIES_COMM_SMALL_BYTES);
-    t->small_recv = fr_alloc<uint8_t>((size_t)FRIES_COMM_SMALL_BYTES * t->size);
-    t->big_send = fr_alloc<uint8_t>(t->big_bytes);
-    t->big_recv = fr_alloc<uint8_t>(t->big_bytes);
+    t->small_send = t->mem.alloc<uint8_t>(FRIES_COMM_SMALL_BYTES);
+    t->small_recv = t->mem.alloc<uint8_t>((size_t)FRIES_COMM_SMALL_BYTES * t->size);
+    t->big_send = t->mem.alloc<uint8_t>(t->big_bytes);
+    t->big_recv = t->mem.alloc<uint8_t>(t->big_bytes);
     FR_HIP(hipMemset(t->small_send, 0, FRIES_COMM_SMALL_BYTES));
     FR_HIP(hipMemset(t->small_recv, 0, (size_t)FRIES_COMM_SMALL_BYTES * t->size));
 }
@@ -205,10 +206,10 @@ extern "C" int fries_hostcomm_create(fries_transport **out, const fries_host_col
         fries_transport *t = new fries_transport();
         t->kind = 3; t->rank = rank; t->size = size; t->device = device; t->big_bytes = big_bytes; t->host = *cb;
         tr_alloc(t);
-        FR_HIP(hipHostMalloc((void **)&t->h_small, FRIES_COMM_SMALL_BYTES, hipHostMallocDefault));
-        FR_HIP(hipHostMalloc((void **)&t->h_small_all, (size_t)FRIES_COMM_SMALL_BYTES * size, hipHostMallocDefault));
-        FR_HIP(hipHostMalloc((void **)&t->h_big_send, big_bytes, hipHostMallocDefault));
-        FR_HIP(hipHostMalloc((void **)&t->h_big_recv, big_bytes, hipHostMallocDefault));
+        t->h_small = t->mem.alloc_pinned<uint8_t>(FRIES_COMM_SMALL_BYTES);
+        t->h_small_all = t->mem.alloc_pinned<uint8_t>((size_t)FRIES_COMM_SMALL_BYTES * size);
+        t->h_big_send = t->mem.alloc_pinned<uint8_t>(big_bytes);
+        t->h_big_recv = t->mem.alloc_pinned<uint8_t>(big_bytes);
         *out = t;
         return 0;
     } catch (const std::exception &e) { fr_set_error(e.what()); return 1; }
@@ -234,7 +235,5 @@ extern "C" void fries_transport_destroy(fries_transport *t) {
     if (!t) return;
     hipSetDevice(t->device);
     if (t->nccl) ncclCommDestroy(t->nccl);
-    hipFree(t->small_send); hipFree(t->small_recv); hipFree(t->big_send); hipFree(t->big_recv);
-    if (t->h_small) { hipHostFree(t->h_small); hipHostFree(t->h_small_all); hipHostFree(t->h_big_send); hipHostFree(t->h_big_recv); }
     delete t;
 }

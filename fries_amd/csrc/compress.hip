@@ -5,16 +5,16 @@
 #include "ctx.hpp"
 #include <cstring>
 
-void fr_vcomp_alloc(FriesCtx *c, uint32_t cap) {
+void fr_vcomp_alloc(FriesCtx *c, DevMem &m, uint32_t cap) {
     VcompBuf &B = c->vc;
-    B.keep = fr_alloc<uint8_t>(cap); B.del = fr_alloc<uint8_t>(cap); B.S = fr_alloc<double>(cap);
-    for (int h = 0; h < 2; h++) { B.psum[h] = fr_alloc<double>(FR_MAX_PART); B.pcnt[h] = fr_alloc<uint32_t>(FR_MAX_PART); }
-    B.state = fr_alloc<CompState>(FR_MAX_ROUNDS + 2);
-    B.teeth = fr_alloc<Teeth>(1);
-    B.dots = fr_alloc<double>(2);
-    B.fix_list = fr_alloc<uint32_t>(FR_MAX_FIX);
-    B.seq.tiles = fr_alloc<SeqRec>(FR_MAX_PART); B.seq.subs = fr_alloc<SeqRec>((size_t)FR_MAX_PART * FR_SUBS_PER_TILE); B.seq.total = fr_alloc<double>(1); B.seq.tsum = fr_alloc<double>(FR_MAX_PART);
-    B.gnorm = fr_alloc<double>(1);
+    B.keep = m.alloc<uint8_t>(cap); B.del = m.alloc<uint8_t>(cap); B.S = m.alloc<double>(cap);
+    for (int h = 0; h < 2; h++) { B.psum[h] = m.alloc<double>(FR_MAX_PART); B.pcnt[h] = m.alloc<uint32_t>(FR_MAX_PART); }
+    B.state = m.alloc<CompState>(FR_MAX_ROUNDS + 2);
+    B.teeth = m.alloc<Teeth>(1);
+    B.dots = m.alloc<double>(2);
+    B.fix_list = m.alloc<uint32_t>(FR_MAX_FIX);
+    B.seq.tiles = m.alloc<SeqRec>(FR_MAX_PART); B.seq.subs = m.alloc<SeqRec>((size_t)FR_MAX_PART * FR_SUBS_PER_TILE); B.seq.total = m.alloc<double>(1); B.seq.tsum = m.alloc<double>(FR_MAX_PART);
+    B.gnorm = m.alloc<double>(1);
     FR_HIP(hipMemsetAsync(B.keep, 0, cap, c->stream));
     FR_HIP(hipMemsetAsync(B.del, 0, cap, c->stream));
     FR_HIP(hipMemsetAsync(B.state, 0, sizeof(CompState) * (FR_MAX_ROUNDS + 2), c->stream));

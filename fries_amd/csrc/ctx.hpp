@@ -17,11 +17,7 @@ void fr_set_error(const std::string &msg);
 
 #define FR_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { throw FriesError(std::string(#call) + ": " + hipGetErrorString(e_)); } } while (0)
 
-template <class T> static inline T *fr_alloc(size_t n) {
-    T *p = nullptr;
-    FR_HIP(hipMalloc((void **)&p, (n ? n : 1) * sizeof(T)));
-    return p;
-}
+#include "devmem.hpp"
 static inline unsigned fr_blocks(size_t n, size_t per) { return (unsigned)((n + per - 1) / per); }
 
 // Optional per-kernel timing with HIP events on the engine's own stream (bench.py's roofline).
@@ -132,6 +128,7 @@ struct FqWork {
 };
 
 struct FriesCtx {
+    DevMem mem;                              // owns every device and pinned array that lives as long as the context (declared first: freed last)
     int device = 0;
     hipStream_t stream = nullptr;
     fries_comm_ops comm{};
@@ -261,21 +258,27 @@ struct FriesCtx {
 };
 
 // vec.hip
-void fr_vec_alloc(FriesCtx *c, VecDev *v, uint32_t cap);
+void fr_vec_alloc(FriesCtx *c, DevMem &m, VecDev *v, uint32_t cap);       // the alloc functions take the owner they allocate from: c->mem, or a caller's scoped DevMem
 void fr_vec_sync_state(FriesCtx *c, VecDev *v, VecState *out);
 void fr_vec_merge(FriesCtx *c, VecDev *v, uint32_t n_spawn_bound, bool same_column, bool arrival_order = false);
 void fr_vec_delete_flagged(FriesCtx *c, VecDev *v, const uint8_t *d_flags, uint32_t n);
 void fr_vec_maybe_rebuild(FriesCtx *c, VecDev *v);
 void fr_vec_reserve_hash(FriesCtx *c, VecDev *v, uint32_t n_new);
-void fr_spawn_alloc(FriesCtx *c, uint32_t cap);
-void fr_xch_alloc(FriesCtx *c, uint32_t cap);
+void fr_spawn_alloc(FriesCtx *c, DevMem &m, uint32_t cap);
+void fr_xch_alloc(FriesCtx *c, DevMem &m, uint32_t cap);
 uint32_t fr_spawn_exchange(FriesCtx *c, uint32_t n_local, int one_pass = 0, bool *merged = nullptr);      // 0: two passes (frisys_mol); 1: one pass, flag inside an integer value; 2: one pass, flag in bit 63 of the index
+// driver.hip: host steps the drivers share
+void fr_spawn_upload_merge(FriesCtx *c, const det_t *det, const double *val, const uint8_t *ini, uint32_t m, bool same_column);
+void fr_spawn_reference_det(FriesCtx *c);
+void fr_driver_prologue(FriesCtx *c, uint32_t seed, bool take_proc_scr, bool take_vec_scr, uint32_t adder_cap);
+void fr_adjust_shift(FriesCtx *c, double glob_norm);
+uint32_t fr_log_err(FriesCtx *c);
 // hbpp.hip
-void fr_hbpp_alloc(FriesCtx *c, uint32_t cap);
+void fr_hbpp_alloc(FriesCtx *c, DevMem &m, uint32_t cap);
 void fr_hbpp_apply(FriesCtx *c, uint32_t n_samp, const double rn[5]);
 void fr_spawn_from_comp(FriesCtx *c);
 // compress.hip
-void fr_vcomp_alloc(FriesCtx *c, uint32_t cap);
+void fr_vcomp_alloc(FriesCtx *c, DevMem &m, uint32_t cap);
 void fr_death_clone(FriesCtx *c, uint32_t vec_size_before);
 void fr_abs_sums(FriesCtx *c);
 void fr_find_preserve(FriesCtx *c, uint32_t *n_samp_io, double *glob_norm);
@@ -285,8 +288,7 @@ const void *fr_dots_enqueue(FriesCtx *c);
 void fr_dots_collect(FriesCtx *c, const void *h_d, double *numer, double *denom);
 void fr_unkept_norm(FriesCtx *c, uint32_t bound);
 // pivotal.hip
-void fr_piv_flat_reserve(FriesCtx *c, uint32_t cap);
-void fr_piv_flat_free(FriesCtx *c);
+void fr_piv_flat_reserve(FriesCtx *c, DevMem &m, uint32_t cap);
 void fr_piv_comp_flat(FriesCtx *c, uint32_t n, uint32_t compress_size);
 void fr_hbpp_piv_apply(FriesCtx *c, uint32_t n_samp, int unit_matrel, uint32_t stage_len[5]);
 void fr_piv_comp(FriesCtx *c, uint32_t compress_size, uint32_t *n_kept, double *glob_norm);
@@ -307,7 +309,7 @@ void fr_hh_stage(FriesCtx *c, int stage, uint32_t n_samp, double rn);
 void fr_hh_ref_ovlp(FriesCtx *c, double out[3]);
 int fr_host_idx_to_proc(const FriesCtx *c, det_t d);
 // system.hip
-void fr_dense_h_setup(FriesCtx *c);      // system.hip
+void fr_dense_h_setup(FriesCtx *c, DevMem &m);
 // enqueue a copy of `bytes` (a multiple of 4, <= 2 KB) at device address src into the readback block; -> host address to read AFTER the next
 // synchronisation of the stream.  The block is a ring: a slot stays valid until ~RB_BYTES more have been asked for.  (vec.hip)
 const void *fr_readback(FriesCtx *c, const void *src, size_t bytes, bool held = false, uint32_t *ticket = nullptr);      // ticket != nullptr: the copy raises a ticket itself (fr_stream_wait_ticket)
@@ -318,7 +320,7 @@ uint32_t fr_ticket_reserve(FriesCtx *c);
 void fr_stream_wait(FriesCtx *c);
 uint32_t fr_stream_ticket(FriesCtx *c);
 void fr_stream_wait_ticket(FriesCtx *c, uint32_t t);
-void fr_rb_init(FriesCtx *c);
+void fr_rb_init(FriesCtx *c, DevMem &m);
 void fr_system_upload(FriesCtx *c, uint32_t n_orb, uint32_t n_elec, const uint8_t *irreps, const double *h_core, const double *eris);
 void fr_h_trial_setup(FriesCtx *c);
 void fr_h_diag_vec(FriesCtx *c, double id_fac, double h_fac);

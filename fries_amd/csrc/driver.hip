@@ -113,6 +113,58 @@ int fr_host_idx_to_proc(const FriesCtx *c, det_t d) {
 }
 
 
+// DistVec::add x m + perform_add from the host: m (determinant, value, initiator flag) triples into the spawn buffers, merged into the
+// vector's own column (same_column) or into column 1 under the initiator rule.  The callers check the capacity and decide what to wait for.
+void fr_spawn_upload_merge(FriesCtx *c, const det_t *det, const double *val, const uint8_t *ini, uint32_t m, bool same_column) {
+    FR_HIP(hipMemcpyAsync(c->sp.det, det, 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
+    FR_HIP(hipMemcpyAsync(c->sp.val, val, 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
+    FR_HIP(hipMemcpyAsync(c->sp.ini, ini, m, hipMemcpyHostToDevice, c->stream));
+    FR_HIP(hipMemcpyAsync(c->sp.n_spawn, &m, 4, hipMemcpyHostToDevice, c->stream));
+    fr_vec_merge(c, &c->vec, m, same_column);
+}
+// the drivers start from 100 x the reference determinant on the rank that owns it
+void fr_spawn_reference_det(FriesCtx *c) {
+    const double v = 100; const uint8_t ini = 1;
+    fr_spawn_upload_merge(c, &c->hf_det, &v, &ini, 1, true);        // perform_add(0) into column 0
+}
+
+// What every driver's setup begins with: the generator seeded, the two scramblers -- proc_scr drawn before vec_scr, and nothing drawn for
+// one the caller supplied where the driver takes it (--load_dir's hash.dat, a host that drew them itself) --, the one-rank send block, the
+// proc scrambler on the device, the Adder's capacity per destination and the owner of the reference determinant (c->hf_det).
+void fr_driver_prologue(FriesCtx *c, uint32_t seed, bool take_proc_scr, bool take_vec_scr, uint32_t adder_cap) {
+    c->mt.seed(seed);
+    c->proc_scr.resize(2 * c->n_orb); c->vec_scr.resize(2 * c->n_orb);
+    if (take_proc_scr && c->in_proc_scr.size() == c->proc_scr.size()) c->proc_scr = c->in_proc_scr; else for (auto &x : c->proc_scr) x = c->mt();
+    if (take_vec_scr && c->in_vec_scr.size() == c->vec_scr.size()) c->vec_scr = c->in_vec_scr; else for (auto &x : c->vec_scr) x = c->mt();
+    c->adder_cap = adder_cap;
+    if (!c->comm.small_send) { c->own_small = c->mem.alloc<uint8_t>(2048); c->comm.small_send = c->own_small; }
+    if (!c->d_proc_scr) c->d_proc_scr = c->mem.alloc<uint32_t>(64);
+    FR_HIP(hipMemcpyAsync(c->d_proc_scr, c->proc_scr.data(), 4 * c->proc_scr.size(), hipMemcpyHostToDevice, c->stream));
+    c->hf_proc = fr_host_idx_to_proc(c, c->hf_det);
+}
+// min(1e6, spawn_length) (frisys_mol.cpp:109-110, frifull_mol.cpp:68-70); FRIES_ADDER_SIZE: a smaller Adder (the DistVec constructor's
+// adder_size) -- the early perform_add rounds at test sizes
+static uint32_t adder_cap_mol(uint32_t spawn_length) {
+    if (getenv("FRIES_ADDER_SIZE")) return (uint32_t)atol(getenv("FRIES_ADDER_SIZE"));
+    return spawn_length > 1000000u ? 1000000u : spawn_length;
+}
+
+// adjust_shift (compress_utils.cpp:684-693) every tenth iteration, as frisys_mol, frifull_mol, frimulti_mol and frisys_hh call it
+void fr_adjust_shift(FriesCtx *c, double glob_norm) {
+    const unsigned shift_interval = 10;
+    const double shift_damping = 0.05;
+    if ((c->iterat + 1) % shift_interval != 0) return;
+    double damp = shift_damping / shift_interval / c->eps;
+    if (c->last_one_norm) { c->en_shift -= damp * log(glob_norm / c->last_one_norm); c->last_one_norm = glob_norm; }
+    if (c->last_one_norm == 0 && glob_norm > c->target_norm) c->last_one_norm = glob_norm;
+}
+// the error word of an iteration's log: the device's flags and the vector state's
+uint32_t fr_log_err(FriesCtx *c) {
+    uint32_t e = 0;
+    FR_HIP(hipMemcpy(&e, c->d_err, 4, hipMemcpyDeviceToHost));
+    return e | c->h_vst.err;
+}
+
 // The first n positions of the vector become the dense (semi-stochastic) space: H inside it is tabulated (fr_dense_h_setup), every rank learns
 // tot_dense_h = sum_mpi(n_determ_h) (frisys_mol.cpp:399: what the matrix sample budget is reduced by) and every rank's n_dense (what
 // DistVec::save writes to dense.txt, vec_utils.hpp:736-745).  zero: init_dense zeroes the values (:876-879), DistVec::load keeps them.
@@ -120,7 +172,7 @@ static void fr_dense_declare(FriesCtx *c, uint32_t n, bool zero) {
     if (n > c->h_vst.curr_size) throw FriesError("dense space larger than the stored vector");
     c->vec.n_dense = n;
     if (n && zero) FR_HIP(hipMemsetAsync(c->vec.v0, 0, 8 * (size_t)n, c->stream));
-    fr_dense_h_setup(c);
+    fr_dense_h_setup(c, c->mem);
     c->n_dense_h_glob = c->n_dense_h;
     c->dense_sizes.assign((size_t)c->n_ranks, n);
     if (c->use_comm) {
@@ -144,26 +196,16 @@ static void frisys_setup(FriesCtx *c, const fries_frisys_params *p) {
     c->vec_nonz = p->vec_nonz; c->mat_nonz = p->mat_nonz; c->new_hb = p->hb_unnorm != 0;
     c->en_shift = 0; c->last_one_norm = 0; c->iterat = 0; c->comp_pending = false;
     if (p->max_dets == 0 || p->mat_nonz == 0 || p->vec_nonz == 0) throw FriesError("max_dets, mat_nonz and vec_nonz must be positive");
-    c->mt.seed(p->seed);
-    c->proc_scr.resize(2 * c->n_orb); c->vec_scr.resize(2 * c->n_orb);
-    if (c->in_proc_scr.size() == c->proc_scr.size()) c->proc_scr = c->in_proc_scr;     // --load_dir: load_proc_hash (frisys_mol.cpp:128-130), no draws
-    else for (auto &x : c->proc_scr) x = c->mt();   // frisys_mol.cpp:133-135
-    for (auto &x : c->vec_scr) x = c->mt();         // :142-144
+    // scramblers: frisys_mol.cpp:133-135, :142-144; --load_dir: load_proc_hash (:128-130), no draws.  Adder: :109-110
+    fr_driver_prologue(c, p->seed, true, false, adder_cap_mol((uint32_t)((uint64_t)p->mat_nonz * 4 / c->n_ranks)));
     // A shard can in principle emit the whole (global) sample budget, so the work arrays are sized for it; the
     // reference sizes them mat_nonz * 4 / n_procs and throws when a shard outgrows that (:109, heat_bathPP.cpp:700-704).
     uint32_t wcap = p->max_dets > p->mat_nonz + 4096 ? p->max_dets : p->mat_nonz + 4096;
-    uint32_t spawn_length = (uint32_t)((uint64_t)p->mat_nonz * 4 / c->n_ranks);
-    c->adder_cap = spawn_length > 1000000u ? 1000000u : spawn_length;        // :109-110
-    if (getenv("FRIES_ADDER_SIZE")) c->adder_cap = (uint32_t)atol(getenv("FRIES_ADDER_SIZE"));      // a smaller Adder (the DistVec constructor's adder_size): the early perform_add rounds at test sizes
-    if (!c->comm.small_send) { c->own_small = fr_alloc<uint8_t>(2048); c->comm.small_send = c->own_small; }
-    if (!c->d_proc_scr) c->d_proc_scr = fr_alloc<uint32_t>(64);
-    FR_HIP(hipMemcpyAsync(c->d_proc_scr, c->proc_scr.data(), 4 * c->proc_scr.size(), hipMemcpyHostToDevice, c->stream));
-    c->hf_proc = fr_host_idx_to_proc(c, c->hf_det);
-    fr_vec_alloc(c, &c->vec, p->max_dets);
-    fr_hbpp_alloc(c, wcap);
-    fr_spawn_alloc(c, p->mat_nonz + 4096);
-    fr_xch_alloc(c, p->mat_nonz + 4096);
-    fr_vcomp_alloc(c, p->max_dets);
+    fr_vec_alloc(c, c->mem, &c->vec, p->max_dets);
+    fr_hbpp_alloc(c, c->mem, wcap);
+    fr_spawn_alloc(c, c->mem, p->mat_nonz + 4096);
+    fr_xch_alloc(c, c->mem, p->mat_nonz + 4096);
+    fr_vcomp_alloc(c, c->mem, p->max_dets);
     if (c->ham_shift_set) c->hf_en = c->ham_shift_hf_en;        // --ham_shift (:95-98)
     fr_h_trial_setup(c);        // replicated: every rank enumerates H * trial (the reference gathers the shards, vec_utils.hpp:920-952)
     if (!c->in_det_space.empty()) {
@@ -177,11 +219,7 @@ static void frisys_setup(FriesCtx *c, const fries_frisys_params *p) {
         if (m > c->sp.cap || m > p->max_dets) throw FriesError("dense space larger than the vector / spawn buffer");
         if (m) {
             std::vector<double> v(m, 1.0); std::vector<uint8_t> f(m, 1);
-            FR_HIP(hipMemcpyAsync(c->sp.det, mine.data(), 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            FR_HIP(hipMemcpyAsync(c->sp.val, v.data(), 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            FR_HIP(hipMemcpyAsync(c->sp.ini, f.data(), m, hipMemcpyHostToDevice, c->stream));
-            FR_HIP(hipMemcpyAsync(c->sp.n_spawn, &m, 4, hipMemcpyHostToDevice, c->stream));
-            fr_vec_merge(c, &c->vec, m, true);
+            fr_spawn_upload_merge(c, mine.data(), v.data(), f.data(), m, true);
         }
         fr_vec_sync_state(c, &c->vec, &c->h_vst);
         fr_dense_declare(c, c->h_vst.curr_size, true);          // (a determinant listed twice takes one position)
@@ -195,23 +233,12 @@ static void frisys_setup(FriesCtx *c, const fries_frisys_params *p) {
         if (m > c->sp.cap) throw FriesError("initial vector larger than the spawn buffer");
         if (m) {
             std::vector<uint8_t> f(m, 1);
-            FR_HIP(hipMemcpyAsync(c->sp.det, d.data(), 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            FR_HIP(hipMemcpyAsync(c->sp.val, v.data(), 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            FR_HIP(hipMemcpyAsync(c->sp.ini, f.data(), m, hipMemcpyHostToDevice, c->stream));
-            FR_HIP(hipMemcpyAsync(c->sp.n_spawn, &m, 4, hipMemcpyHostToDevice, c->stream));
-            fr_vec_merge(c, &c->vec, m, true);
+            fr_spawn_upload_merge(c, d.data(), v.data(), f.data(), m, true);
             FR_HIP(hipStreamSynchronize(c->stream));
         }
     }
     // start from 100 * |HF> on the rank that owns it (:277-281)
-    else if (c->rank == c->hf_proc) {
-        double v = 100; uint8_t one = 1; uint32_t n1 = 1;
-        FR_HIP(hipMemcpyAsync(c->sp.det, &c->hf_det, 8, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.val, &v, 8, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.ini, &one, 1, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.n_spawn, &n1, 4, hipMemcpyHostToDevice, c->stream));
-        fr_vec_merge(c, &c->vec, 1, true);               // perform_add(0) into column 0
-    }
+    else if (c->rank == c->hf_proc) fr_spawn_reference_det(c);
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     check_dev_err(c);
 }
@@ -315,13 +342,7 @@ static void frisys_iterate(FriesCtx *c, fries_iter_log *lg) {
     if (c->n_dense_h_glob || c->vec.n_dense) glob_norm += fr_dense_norm_all(c);       // glob_norm += sol_vec.dense_norm() (:503)
     c->glob_norm = glob_norm;
     c->nkept = c->vec_nonz - n_samp;
-    const unsigned shift_interval = 10;
-    const double shift_damping = 0.05;
-    if ((c->iterat + 1) % shift_interval == 0) {     // adjust_shift, compress_utils.cpp:684-693
-        double damp = shift_damping / shift_interval / c->eps;
-        if (c->last_one_norm) { c->en_shift -= damp * log(glob_norm / c->last_one_norm); c->last_one_norm = glob_norm; }
-        if (c->last_one_norm == 0 && glob_norm > c->target_norm) c->last_one_norm = glob_norm;
-    }
+    fr_adjust_shift(c, glob_norm);
     double rn_sys = uni(c->mt);
     fr_sys_comp(c, n_samp, rn_sys);
     c->iterat++;
@@ -335,9 +356,7 @@ static void frisys_iterate(FriesCtx *c, fries_iter_log *lg) {
         lg->nkept = c->nkept; lg->n_nonz = c->h_vst.n_nonz; lg->curr_size = c->h_vst.curr_size;
         lg->num_success = c->num_success;
         for (int k = 0; k < 5; k++) lg->comp_len[k] = c->comp_len[k];
-        uint32_t e = 0;
-        FR_HIP(hipMemcpy(&e, c->d_err, 4, hipMemcpyDeviceToHost));
-        lg->err = e | c->h_vst.err;
+        lg->err = fr_log_err(c);
     }
 }
 
@@ -348,44 +367,28 @@ static void frifull_setup(FriesCtx *c, const fries_frifull_params *p) {
     c->eps = p->epsilon; c->target_norm = p->target_norm; c->init_thresh = 0;
     c->vec_nonz = p->vec_nonz; c->mat_nonz = 0; c->full_mode = true;
     c->en_shift = 0; c->last_one_norm = 0; c->iterat = 0;
-    c->mt.seed(p->seed);
-    c->proc_scr.resize(2 * c->n_orb); c->vec_scr.resize(2 * c->n_orb);
-    for (auto &x : c->proc_scr) x = c->mt();        // frifull_mol.cpp:96-98
-    for (auto &x : c->vec_scr) x = c->mt();         // :104-107
-    if (!c->comm.small_send) { c->own_small = fr_alloc<uint8_t>(2048); c->comm.small_send = c->own_small; }
     uint32_t scap = p->spawn_cap ? p->spawn_cap : 8000000u;
     if (scap > 8000000u) scap = 8000000u;           // one merge handles FR_MAX_PART tiles of spawns
     {   // frifull_mol.cpp:68-70: the Adder holds min(1e6, target_nonz / n_procs * num_ex / n_procs / 4) elements per destination (32-bit arithmetic there)
         const uint32_t nv = c->n_orb - c->n_elec / 2;
         const uint32_t num_ex = c->n_elec * c->n_elec * nv * nv;
         const uint32_t spawn_len = p->vec_nonz / (uint32_t)c->n_ranks * num_ex / (uint32_t)c->n_ranks / 4u;
-        c->adder_cap = spawn_len > 1000000u ? 1000000u : spawn_len;
-        if (getenv("FRIES_ADDER_SIZE")) c->adder_cap = (uint32_t)atol(getenv("FRIES_ADDER_SIZE"));
+        fr_driver_prologue(c, p->seed, false, false, adder_cap_mol(spawn_len));     // both scramblers always drawn (frifull_mol.cpp:96-98, :104-107)
     }
-    if (!c->d_proc_scr) c->d_proc_scr = fr_alloc<uint32_t>(64);
-    FR_HIP(hipMemcpyAsync(c->d_proc_scr, c->proc_scr.data(), 4 * c->proc_scr.size(), hipMemcpyHostToDevice, c->stream));
-    c->hf_proc = fr_host_idx_to_proc(c, c->hf_det);
-    fr_vec_alloc(c, &c->vec, p->max_dets);
-    fr_spawn_alloc(c, scap);
-    fr_xch_alloc(c, scap);
-    fr_vcomp_alloc(c, p->max_dets);
-    c->W.kin = fr_alloc<uint32_t>(p->max_dets);     // sys_comp's tooth-index scratch (the HB-PP arrays are not allocated here)
-    if (!c->d_norms_keep) { c->d_norms_keep = fr_alloc<double>(FR_MAX_RANKS); c->d_seq_scratch = fr_alloc<double>(1); }        // sys_comp over ranks: the other ranks' norms, the second in-order sum
+    fr_vec_alloc(c, c->mem, &c->vec, p->max_dets);
+    fr_spawn_alloc(c, c->mem, scap);
+    fr_xch_alloc(c, c->mem, scap);
+    fr_vcomp_alloc(c, c->mem, p->max_dets);
+    c->W.kin = c->mem.alloc<uint32_t>(p->max_dets);     // sys_comp's tooth-index scratch (the HB-PP arrays are not allocated here)
+    if (!c->d_norms_keep) { c->d_norms_keep = c->mem.alloc<double>(FR_MAX_RANKS); c->d_seq_scratch = c->mem.alloc<double>(1); }        // sys_comp over ranks: the other ranks' norms, the second in-order sum
     // trial vector = HF (:121-147); there is no H * trial in this driver
     c->n_trial = 1; c->n_htrial = 0;
-    c->tr_det = fr_alloc<det_t>(1); c->tr_val = fr_alloc<double>(1);
-    c->htr_det = fr_alloc<det_t>(1); c->htr_val = fr_alloc<double>(1);
+    c->tr_det = c->mem.alloc<det_t>(1); c->tr_val = c->mem.alloc<double>(1);
+    c->htr_det = c->mem.alloc<det_t>(1); c->htr_val = c->mem.alloc<double>(1);
     double one = 1.0;
     FR_HIP(hipMemcpyAsync(c->tr_det, &c->hf_det, 8, hipMemcpyHostToDevice, c->stream));
     FR_HIP(hipMemcpyAsync(c->tr_val, &one, 8, hipMemcpyHostToDevice, c->stream));
-    if (c->rank == (int)c->hf_proc) {   // start from 100 * |HF> on the rank that owns it (:186-190)
-        double v = 100; uint8_t ini = 1; uint32_t n1 = 1;
-        FR_HIP(hipMemcpyAsync(c->sp.det, &c->hf_det, 8, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.val, &v, 8, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.ini, &ini, 1, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.n_spawn, &n1, 4, hipMemcpyHostToDevice, c->stream));
-        fr_vec_merge(c, &c->vec, 1, true);
-    }
+    if (c->rank == (int)c->hf_proc) fr_spawn_reference_det(c);      // start from 100 * |HF> on the rank that owns it (:186-190)
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     check_dev_err(c);
 }
@@ -403,13 +406,7 @@ static void frifull_iterate(FriesCtx *c, fries_iter_log *lg) {
     fr_find_preserve(c, &n_samp, &glob_norm);         // :263-264
     c->glob_norm = glob_norm;
     c->nkept = c->vec_nonz - n_samp;
-    const unsigned shift_interval = 10;
-    const double shift_damping = 0.05;
-    if ((c->iterat + 1) % shift_interval == 0) {     // :272-278
-        double damp = shift_damping / shift_interval / c->eps;
-        if (c->last_one_norm) { c->en_shift -= damp * log(glob_norm / c->last_one_norm); c->last_one_norm = glob_norm; }
-        if (c->last_one_norm == 0 && glob_norm > c->target_norm) c->last_one_norm = glob_norm;
-    }
+    fr_adjust_shift(c, glob_norm);                    // :272-278
     double rn_sys = uni(c->mt);
     fr_sys_comp(c, n_samp, rn_sys);                   // :283-289 (an element leaves the table only when it is zero in both columns)
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
@@ -429,9 +426,7 @@ static void frifull_iterate(FriesCtx *c, fries_iter_log *lg) {
         lg->nkept = c->nkept; lg->n_nonz = c->h_vst.n_nonz; lg->curr_size = c->h_vst.curr_size;
         lg->num_success = c->num_success;
         for (int k = 0; k < 5; k++) lg->comp_len[k] = 0;
-        uint32_t e = 0;
-        FR_HIP(hipMemcpy(&e, c->d_err, 4, hipMemcpyDeviceToHost));
-        lg->err = e | c->h_vst.err;
+        lg->err = fr_log_err(c);
     }
 }
 
@@ -519,7 +514,7 @@ extern "C" int fries_ctx_create(fries_ctx **out, int device) {
         if (getenv("FRIES_FKS_GRID")) h->c.fks_grid = (unsigned)atoi(getenv("FRIES_FKS_GRID"));
     }
     FR_HIP(hipStreamCreate(&h->c.stream));
-    h->c.d_err = fr_alloc<uint32_t>(1);
+    h->c.d_err = h->c.mem.alloc<uint32_t>(1);
     FR_HIP(hipMemset(h->c.d_err, 0, 4));
     *out = h;
     FR_API_END
@@ -527,65 +522,20 @@ extern "C" int fries_ctx_create(fries_ctx **out, int device) {
 
 extern "C" void fries_ctx_destroy(fries_ctx *h) {
     if (!h) return;
-    hipSetDevice(h->c.device);
+    FriesCtx &c = h->c;
+    hipSetDevice(c.device);
     hipDeviceSynchronize();
-    // device allocations are released with the context's device memory pool at process exit;
-    // explicit frees for the large arrays:
-    VecDev &v = h->c.vec;
-    hipFree(v.dets); hipFree(v.v0); hipFree(v.v1); hipFree(v.diag); hipFree(v.active); hipFree(v.free_stack); hipFree(v.hs); hipFree(v.stat_part); hipFree(v.st);
-    CompWork &W = h->c.W;
-    for (int k = 0; k < 2; k++) { hipFree(W.el[k].val); hipFree(W.el[k].pos); hipFree(W.el[k].code); hipFree(W.el[k].ndiv); hipFree(W.el[k].nsub); hipFree(W.el[k].rinv); hipFree(W.el[k].raux); hipFree(W.el[k].det); hipFree(W.psum[k]); hipFree(W.pcnt[k]); }
-    hipFree(W.wt_remain); hipFree(W.keep); hipFree(W.S); hipFree(W.kin); hipFree(W.cnt); hipFree(W.e_wi); hipFree(W.e_sub); hipFree(W.e_val); hipFree(W.state); hipFree(W.teeth); hipFree(W.fix_list);
-    if (h->c.stg_mem) { hipFree(h->c.stg_mem); hipFree(h->c.spill_mem); hipFree(h->c.spill_cnt_mem); hipFree(h->c.tile_dirty_mem); }
-    {
-        FriesCtx &c = h->c;
-        if (c.dbg >= 1 && c.n_fks_sequential) {
-            FksSqCtl hc{};
-            hipMemcpy(&hc, c.fsq.ctl, sizeof(hc), hipMemcpyDeviceToHost);
-            fprintf(stderr, "[fries] find_keep_sub in the reference's order: %llu stages; %llu guess rounds, %llu exact rounds over %llu tiles (touched tiles taken as one integer step: %llu, element by element: %llu), %llu walks over %llu tiles\n",
-                    (unsigned long long)c.n_fks_sequential, (unsigned long long)c.n_fsq_guess, (unsigned long long)c.n_fsq_exact, (unsigned long long)c.n_fsq_chain_tiles,
-                    hc.n_fast, hc.n_dense, (unsigned long long)c.n_fsq_walk, (unsigned long long)c.n_fsq_walk_tiles);
-        }
-        FksSq &SQ = c.fsq;
-        hipFree(SQ.dl); hipFree(SQ.nwr); hipFree(SQ.nkp); hipFree(SQ.gb); hipFree(SQ.lb); hipFree(SQ.dgb); hipFree(SQ.kb); hipFree(SQ.dk);
-        hipFree(SQ.tk); hipFree(SQ.tkx); hipFree(SQ.tg); hipFree(SQ.tgx); hipFree(SQ.tany);
-        hipFree(SQ.mG); hipFree(SQ.mL); hipFree(SQ.sabs); hipFree(SQ.gt); hipFree(SQ.lt); hipFree(SQ.eG); hipFree(SQ.eL); hipFree(SQ.mflag); hipFree(SQ.fast);
-        if (SQ.gb2) { hipFree(SQ.gb2); hipFree(SQ.lb2); }
-        hipFree(SQ.ctl);
+    if (c.dbg >= 1 && c.n_fks_sequential) {
+        FksSqCtl hc{};
+        hipMemcpy(&hc, c.fsq.ctl, sizeof(hc), hipMemcpyDeviceToHost);
+        fprintf(stderr, "[fries] find_keep_sub in the reference's order: %llu stages; %llu guess rounds, %llu exact rounds over %llu tiles (touched tiles taken as one integer step: %llu, element by element: %llu), %llu walks over %llu tiles\n",
+                (unsigned long long)c.n_fks_sequential, (unsigned long long)c.n_fsq_guess, (unsigned long long)c.n_fsq_exact, (unsigned long long)c.n_fsq_chain_tiles,
+                hc.n_fast, hc.n_dense, (unsigned long long)c.n_fsq_walk, (unsigned long long)c.n_fsq_walk_tiles);
     }
-    {   // the find_keep_sub replay's arrays (allocated with the work arrays: hbpp.hip)
-        Fks2Work &F = h->c.F2;
-        if (F.dk8) {
-            hipFree(F.dk8); hipFree(F.dg8); hipFree(F.ws8); hipFree(F.cdirty); hipFree(F.wrec); hipFree(F.wNp);
-            hipFree(F.xk8); hipFree(F.xg8); hipFree(F.scal); hipFree(F.hist); hipFree(F.ck); hipFree(F.cg); hipFree(F.cw); hipFree(F.ckx); hipFree(F.cgx); hipFree(F.dbg_cnt);
-            hipFree(h->c.fks_wkx); hipFree(h->c.fks_wgx); hipFree(h->c.fks_wk); hipFree(h->c.fks_wg); hipFree(h->c.fks_sxk8); hipFree(h->c.fks_sxg8); hipFree(h->c.fks_saved);
-        }
-    }
-    hipFree(h->c.c_pos); hipFree(h->c.c_orbs); hipFree(h->c.c_val); hipFree(h->c.d_nsucc);
-    SpawnBuf &s = h->c.sp;
-    hipFree(s.det); hipFree(s.val); hipFree(s.ini); hipFree(s.slot); hipFree(s.flag);
-    if (s.bdet) { hipFree(s.bdet); hipFree(s.bval); hipFree(s.bini); hipFree(s.bn); hipFree(s.xbounds); }
-    for (int k = 0; k < 2; k++) { hipFree(s.key[k]); hipFree(s.pay[k]); }
-    hipFree(s.hist); hipFree(s.pcnt); hipFree(s.n_spawn);
-    VcompBuf &b = h->c.vc;
-    hipFree(b.keep); hipFree(b.del); hipFree(b.S);
-    for (int k = 0; k < 2; k++) { hipFree(b.psum[k]); hipFree(b.pcnt[k]); }
-    hipFree(b.state); hipFree(b.teeth); hipFree(b.dots); hipFree(b.fix_list);
-    PivBuf &pv = h->c.piv;
-    if (pv.start) { hipFree(pv.start); hipFree(pv.carry); hipFree(pv.U); hipFree(pv.unit); hipFree(pv.scal); hipFree(pv.tile_dd); hipFree(pv.tile_nz); hipFree(pv.nz_start); }
-    hipFree(h->c.d_dh_from); hipFree(h->c.d_dh_to); hipFree(h->c.d_dh_el); hipFree(h->c.d_dense_norm);
-    hipFree(h->c.d_h); hipFree(h->c.d_eris); hipFree(h->c.d_hb); hipFree(h->c.d_err);
-    if (h->c.full_cnt) { hipFree(h->c.full_cnt); hipFree(h->c.full_nz); hipFree(h->c.full_off); hipFree(h->c.full_list); }
-    fr_piv_flat_free(&h->c);
-    if (h->c.pv_goff) hipFree(h->c.pv_goff);
-    if (h->c.hh_fdet) hipFree(h->c.hh_fdet);
-    if (h->c.hh_ovlp) hipFree(h->c.hh_ovlp);
-    if (h->c.h_fks) hipHostFree(h->c.h_fks);
-    if (h->c.h_rb) hipHostFree(h->c.h_rb);
-    if (h->c.hhf_cnt) hipFree(h->c.hhf_cnt);
-    hipFree(h->c.tr_det); hipFree(h->c.tr_val); hipFree(h->c.htr_det); hipFree(h->c.htr_val);
-    if (h->c.stream) hipStreamDestroy(h->c.stream);
-    delete h;
+    for (hipEvent_t e : c.prof_pool) hipEventDestroy(e);
+    for (ProfSpan &sp : c.prof_spans) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
+    if (c.stream) hipStreamDestroy(c.stream);
+    delete h;       // c.mem frees every device and pinned array the context allocated
 }
 
 extern "C" int fries_set_comm(fries_ctx *h, const fries_comm *cm) {
@@ -680,8 +630,8 @@ extern "C" int fries_tie_margins(fries_ctx *h, int enable, double *fks_min_rel, 
         FR_HIP(hipStreamSynchronize(c->stream));
     }
     else { if (fks_min_rel) *fks_min_rel = INFINITY; if (fp_min_rel) *fp_min_rel = INFINITY; }
-    if (enable && !c->d_tie) { c->d_tie = fr_alloc<uint32_t>(2); FR_HIP(hipMemcpy(c->d_tie, inf2, 8, hipMemcpyHostToDevice)); }
-    if (!enable && c->d_tie) { FR_HIP(hipFree(c->d_tie)); c->d_tie = nullptr; }
+    if (enable && !c->d_tie) { c->d_tie = c->mem.alloc<uint32_t>(2); FR_HIP(hipMemcpy(c->d_tie, inf2, 8, hipMemcpyHostToDevice)); }
+    if (!enable) c->mem.release(c->d_tie);
     FR_API_END
 }
 extern "C" int fries_set_proc_scrambler(fries_ctx *h, const uint32_t *proc_scr, size_t n) {
@@ -709,14 +659,14 @@ extern "C" int fries_matrel_batch(fries_ctx *h, int kind, const uint64_t *dets, 
     FR_HIP(hipSetDevice(c->device));
     if (!c->d_eris) throw FriesError("fries_set_molecule must be called first");
     if (n == 0) return 0;
-    det_t *dd = fr_alloc<det_t>(n); uint8_t *dob = fr_alloc<uint8_t>(4 * n); double *dout = fr_alloc<double>(n); int32_t *ds = fr_alloc<int32_t>(n);
+    DevMem tmp;
+    det_t *dd = tmp.alloc<det_t>(n); uint8_t *dob = tmp.alloc<uint8_t>(4 * n); double *dout = tmp.alloc<double>(n); int32_t *ds = tmp.alloc<int32_t>(n);
     FR_HIP(hipMemcpy(dd, dets, 8 * n, hipMemcpyHostToDevice));
     if (orbs) FR_HIP(hipMemcpy(dob, orbs, 4 * n, hipMemcpyHostToDevice));
     FR_LAUNCH(c, "k_matrel_batch", k_matrel_batch, dim3(fr_blocks(n, FR_BLOCK)), dim3(FR_BLOCK), kind, dd, orbs ? dob : nullptr, n, c->d_h, c->d_eris, c->n_orb, dout, ds);
     FR_HIP(hipStreamSynchronize(c->stream));
     FR_HIP(hipMemcpy(out, dout, 8 * n, hipMemcpyDeviceToHost));
     if (sign) FR_HIP(hipMemcpy(sign, ds, 4 * n, hipMemcpyDeviceToHost));
-    hipFree(dd); hipFree(dob); hipFree(dout); hipFree(ds);
     FR_API_END
 }
 
@@ -813,12 +763,15 @@ extern "C" int fries_vec_download(fries_ctx *h, uint64_t *dets, double *vals, si
     FR_API_END
 }
 
+static void need_column(int column) {
+    if (column != 0 && column != 1) throw FriesError("column must be 0 or 1");
+}
 // ---- column mirrors for hosts that keep DistVec::values() / operator[] / matr_el_at_pos pointer semantics (include/FRIES/vec_utils.hpp)
 extern "C" int fries_vec_column_download(fries_ctx *h, int column, double *out, size_t cap, size_t *n) {
     FR_API_BEGIN
     FriesCtx *c = &h->c;
     FR_HIP(hipSetDevice(c->device));
-    if (column != 0 && column != 1) throw FriesError("column must be 0 or 1");
+    need_column(column);
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     size_t m = c->h_vst.curr_size;
     if (n) *n = m;
@@ -830,7 +783,7 @@ extern "C" int fries_vec_column_upload(fries_ctx *h, int column, const double *i
     FR_API_BEGIN
     FriesCtx *c = &h->c;
     FR_HIP(hipSetDevice(c->device));
-    if (column != 0 && column != 1) throw FriesError("column must be 0 or 1");
+    need_column(column);
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     if (n > c->h_vst.curr_size) throw FriesError("more values than stored positions");
     if (n) FR_HIP(hipMemcpy(column ? c->vec.v1 : c->vec.v0, in, 8 * n, hipMemcpyHostToDevice));
@@ -840,7 +793,7 @@ extern "C" int fries_vec_column_zero(fries_ctx *h, int column) {
     FR_API_BEGIN
     FriesCtx *c = &h->c;
     FR_HIP(hipSetDevice(c->device));
-    if (column != 0 && column != 1) throw FriesError("column must be 0 or 1");
+    need_column(column);
     FR_HIP(hipMemsetAsync(column ? c->vec.v1 : c->vec.v0, 0, 8 * (size_t)c->vec.cap, c->stream));      // DistVec::zero_vec: the whole row (vec_utils.hpp:577-579)
     FR_API_END
 }
@@ -854,7 +807,7 @@ extern "C" int fries_vec_add_vecs(fries_ctx *h, int idx1, int idx2, double cf) {
     FR_API_BEGIN
     FriesCtx *c = &h->c;
     FR_HIP(hipSetDevice(c->device));
-    if ((idx1 != 0 && idx1 != 1) || (idx2 != 0 && idx2 != 1)) throw FriesError("column must be 0 or 1");
+    need_column(idx1); need_column(idx2);
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     const uint32_t m = c->h_vst.curr_size;
     if (m) FR_LAUNCH(c, "k_add_vecs", k_add_vecs, dim3(fr_blocks(m, FR_BLOCK) > 2048 ? 2048 : fr_blocks(m, FR_BLOCK)), dim3(FR_BLOCK), c->vec, idx1, idx2, cf);
@@ -909,17 +862,17 @@ extern "C" int fries_vec_dot_list(fries_ctx *h, int column, const uint64_t *dets
     FR_API_BEGIN
     FriesCtx *c = &h->c;
     FR_HIP(hipSetDevice(c->device));
-    if (column != 0 && column != 1) throw FriesError("column must be 0 or 1");
+    need_column(column);
     if (n > 0xffffffffull) throw FriesError("list too long");
     double r = 0;
     if (n) {
-        det_t *dd = fr_alloc<det_t>(n); double *dw = fr_alloc<double>(n + 1);
+        DevMem tmp;
+        det_t *dd = tmp.alloc<det_t>(n); double *dw = tmp.alloc<double>(n + 1);
         FR_HIP(hipMemcpy(dd, dets, 8 * n, hipMemcpyHostToDevice));
         FR_HIP(hipMemcpy(dw, vals, 8 * n, hipMemcpyHostToDevice));
         FR_LAUNCH(c, "k_dot_list", k_dot_list, dim3(1), dim3(FR_BLOCK), c->vec, column, dd, dw, (uint32_t)n, dw + n);
         FR_HIP(hipStreamSynchronize(c->stream));
         FR_HIP(hipMemcpy(&r, dw + n, 8, hipMemcpyDeviceToHost));
-        hipFree(dd); hipFree(dw);
     }
     if (out) *out = r;
     FR_API_END
@@ -936,23 +889,22 @@ extern "C" int fries_htrial_download(fries_ctx *h, uint64_t *dets, double *vals,
     FR_API_END
 }
 
+// DistVec::add drops zero values before they reach the adder (vec_utils.hpp:418-423)
+struct HostAdds {
+    std::vector<det_t> d; std::vector<double> v; std::vector<uint8_t> f; uint32_t m;
+    HostAdds(const uint64_t *dets, const double *vals, const uint8_t *ini, size_t n) {
+        for (size_t i = 0; i < n; i++) if (vals[i] != 0) { d.push_back(dets[i]); v.push_back(vals[i]); f.push_back(ini[i]); }
+        m = (uint32_t)d.size();
+    }
+};
 extern "C" int fries_vec_add(fries_ctx *h, const uint64_t *dets, const double *vals, const uint8_t *ini, size_t n) {
     FR_API_BEGIN
     FriesCtx *c = &h->c;
     FR_HIP(hipSetDevice(c->device));
     if (n > c->sp.cap) throw FriesError("Too many elements added to Adder - must call perform_add() more frequently.");
     if (c->use_comm) throw FriesError("fries_vec_add is a one-rank entry point; with ranks, adds travel inside fries_frisys_iterate");
-    // DistVec::add drops zero values before they reach the adder (vec_utils.hpp:418-423)
-    std::vector<det_t> d; std::vector<double> v; std::vector<uint8_t> f;
-    for (size_t i = 0; i < n; i++) if (vals[i] != 0) { d.push_back(dets[i]); v.push_back(vals[i]); f.push_back(ini[i]); }
-    uint32_t m = (uint32_t)d.size();
-    if (m) {
-        FR_HIP(hipMemcpyAsync(c->sp.det, d.data(), 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.val, v.data(), 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.ini, f.data(), m, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.n_spawn, &m, 4, hipMemcpyHostToDevice, c->stream));
-        fr_vec_merge(c, &c->vec, m, true);
-    }
+    const HostAdds a(dets, vals, ini, n);
+    if (a.m) fr_spawn_upload_merge(c, a.d.data(), a.v.data(), a.f.data(), a.m, true);
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     check_dev_err(c);
     FR_API_END
@@ -964,19 +916,13 @@ extern "C" int fries_vec_add_to(fries_ctx *h, int column, const uint64_t *dets, 
     FR_API_BEGIN
     FriesCtx *c = &h->c;
     FR_HIP(hipSetDevice(c->device));
-    if (column != 0 && column != 1) throw FriesError("column must be 0 or 1");
+    need_column(column);
     if (n > c->sp.cap) throw FriesError("Too many elements added to Adder - must call perform_add() more frequently.");
-    std::vector<det_t> d; std::vector<double> v; std::vector<uint8_t> f;
-    for (size_t i = 0; i < n; i++) if (vals[i] != 0) { d.push_back(dets[i]); v.push_back(vals[i]); f.push_back(ini[i]); }
-    uint32_t m = (uint32_t)d.size();
-    if (m) {
+    const HostAdds a(dets, vals, ini, n);
+    if (a.m) {
         fr_vec_sync_state(c, &c->vec, &c->h_vst);
         fr_vec_maybe_rebuild(c, &c->vec);           // tombstones of earlier deletes (the fused loop does this once per iteration)
-        FR_HIP(hipMemcpyAsync(c->sp.det, d.data(), 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.val, v.data(), 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.ini, f.data(), m, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.n_spawn, &m, 4, hipMemcpyHostToDevice, c->stream));
-        fr_vec_merge(c, &c->vec, m, column == 0);
+        fr_spawn_upload_merge(c, a.d.data(), a.v.data(), a.f.data(), a.m, column == 0);
     }
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     check_dev_err(c);
@@ -1129,7 +1075,7 @@ extern "C" int fries_vec_set_dense(fries_ctx *h, uint32_t n_dense) {
     FriesCtx *c = &h->c;
     FR_HIP(hipSetDevice(c->device));
     if (!c->vec.dets || c->hh_mode || c->fq_mode || c->full_mode) throw FriesError("fries_vec_set_dense needs a frisys_mol context (after fries_frisys_setup and fries_vec_load)");
-    if (c->d_dh_from) { hipFree(c->d_dh_from); hipFree(c->d_dh_to); hipFree(c->d_dh_el); c->d_dh_from = nullptr; c->d_dh_to = nullptr; c->d_dh_el = nullptr; }
+    c->mem.release(c->d_dh_from); c->mem.release(c->d_dh_to); c->mem.release(c->d_dh_el);
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     fr_dense_declare(c, n_dense, false);
     check_dev_err(c);
@@ -1144,6 +1090,15 @@ extern "C" int fries_dense_sizes(fries_ctx *h, uint32_t *sizes, size_t cap, size
     FR_API_END
 }
 
+// the compression result (c_pos / c_orbs / c_val, num_success entries) to the host arrays that were asked for
+static void comp_copy_out(FriesCtx *c, uint32_t *det_pos, uint8_t *orbs, double *vals, size_t cap, bool sync_first = false) {
+    const size_t m = c->num_success;
+    if (cap < m) throw FriesError("output buffer too small");
+    if (sync_first) FR_HIP(hipStreamSynchronize(c->stream));
+    if (det_pos) FR_HIP(hipMemcpy(det_pos, c->c_pos, 4 * m, hipMemcpyDeviceToHost));
+    if (orbs) FR_HIP(hipMemcpy(orbs, c->c_orbs, 4 * m, hipMemcpyDeviceToHost));
+    if (vals) FR_HIP(hipMemcpy(vals, c->c_val, 8 * m, hipMemcpyDeviceToHost));
+}
 extern "C" int fries_apply_hbpp_sys(fries_ctx *h, uint32_t n_samp, const double rn[5], int unit_matrel,
                                     uint32_t *det_pos, uint8_t *orbs, double *vals, size_t cap, size_t *n_out, uint32_t comp_len[5]) {
     FR_API_BEGIN
@@ -1157,10 +1112,7 @@ extern "C" int fries_apply_hbpp_sys(fries_ctx *h, uint32_t n_samp, const double 
     if (comp_len) for (int k = 0; k < 5; k++) comp_len[k] = c->comp_len[k];
     check_dev_err(c);
     c->comp_pending = true;     // the result stays in c_pos / c_orbs / c_val / d_nsucc for fries_spawn_from_comp and fries_comp_download
-    if (cap < m) throw FriesError("output buffer too small");
-    if (det_pos) FR_HIP(hipMemcpy(det_pos, c->c_pos, 4 * m, hipMemcpyDeviceToHost));
-    if (orbs) FR_HIP(hipMemcpy(orbs, c->c_orbs, 4 * m, hipMemcpyDeviceToHost));
-    if (vals) FR_HIP(hipMemcpy(vals, c->c_val, 8 * m, hipMemcpyDeviceToHost));
+    comp_copy_out(c, det_pos, orbs, vals, cap);
     FR_API_END
 }
 
@@ -1179,10 +1131,7 @@ extern "C" int fries_apply_hbpp_piv(fries_ctx *h, uint32_t n_samp, int unit_matr
     if (stage_len) for (int k = 0; k < 5; k++) stage_len[k] = sl[k];
     check_dev_err(c);
     c->comp_pending = true;
-    if (cap < m) throw FriesError("output buffer too small");
-    if (det_pos) FR_HIP(hipMemcpy(det_pos, c->c_pos, 4 * m, hipMemcpyDeviceToHost));
-    if (orbs) FR_HIP(hipMemcpy(orbs, c->c_orbs, 4 * m, hipMemcpyDeviceToHost));
-    if (vals) FR_HIP(hipMemcpy(vals, c->c_val, 8 * m, hipMemcpyDeviceToHost));
+    comp_copy_out(c, det_pos, orbs, vals, cap);
     FR_API_END
 }
 
@@ -1240,11 +1189,7 @@ extern "C" int fries_comp_download(fries_ctx *h, uint32_t *det_pos, uint8_t *orb
     FR_HIP(hipSetDevice(c->device));
     const size_t m = c->num_success;
     if (n_out) *n_out = m;
-    if (cap < m) throw FriesError("output buffer too small");
-    FR_HIP(hipStreamSynchronize(c->stream));
-    if (det_pos) FR_HIP(hipMemcpy(det_pos, c->c_pos, 4 * m, hipMemcpyDeviceToHost));
-    if (orbs) FR_HIP(hipMemcpy(orbs, c->c_orbs, 4 * m, hipMemcpyDeviceToHost));
-    if (vals) FR_HIP(hipMemcpy(vals, c->c_val, 8 * m, hipMemcpyDeviceToHost));
+    comp_copy_out(c, det_pos, orbs, vals, cap, true);
     FR_API_END
 }
 
@@ -1327,9 +1272,10 @@ extern "C" int fries_test_teeth(fries_ctx *h, double r0, double unit, uint32_t n
     FR_API_BEGIN
     FriesCtx *c = &h->c;
     FR_HIP(hipSetDevice(c->device));
-    Teeth *t = fr_alloc<Teeth>(1);
-    double *dp = fr_alloc<double>(n), *dq = fr_alloc<double>(nq);
-    uint32_t *db = fr_alloc<uint32_t>(nq);
+    DevMem tmp;
+    Teeth *t = tmp.alloc<Teeth>(1);
+    double *dp = tmp.alloc<double>(n), *dq = tmp.alloc<double>(nq);
+    uint32_t *db = tmp.alloc<uint32_t>(nq);
     if (nq) FR_HIP(hipMemcpy(dq, query, 8 * (size_t)nq, hipMemcpyHostToDevice));
     FR_LAUNCH(c, "k_test_teeth", k_test_teeth, dim3(1), dim3(1), t, r0, unit, n, dp, dq, nq, db);
     uint32_t m = n > nq ? n : nq;
@@ -1337,7 +1283,6 @@ extern "C" int fries_test_teeth(fries_ctx *h, double r0, double unit, uint32_t n
     FR_HIP(hipStreamSynchronize(c->stream));
     if (n) FR_HIP(hipMemcpy(out_pos, dp, 8 * (size_t)n, hipMemcpyDeviceToHost));
     if (nq) FR_HIP(hipMemcpy(out_below, db, 4 * (size_t)nq, hipMemcpyDeviceToHost));
-    hipFree(t); hipFree(dp); hipFree(dq); hipFree(db);
     FR_API_END
 }
 
@@ -1361,13 +1306,14 @@ extern "C" int fries_test_seqsum(fries_ctx *h, const double *vals, uint32_t n, d
     FR_HIP(hipSetDevice(c->device));
     unsigned ntile = fr_blocks(n ? n : 1, FR_SEQ_TILE);
     if (ntile > FR_MAX_PART) throw FriesError("too many elements");
+    DevMem tmp;
     SeqWork Q;
-    Q.tiles = fr_alloc<SeqRec>(ntile); Q.subs = fr_alloc<SeqRec>((size_t)ntile * FR_SUBS_PER_TILE); Q.total = fr_alloc<double>(1); Q.tsum = fr_alloc<double>(ntile);
-    double *da = fr_alloc<double>(n), *dout = fr_alloc<double>(n);
+    Q.tiles = tmp.alloc<SeqRec>(ntile); Q.subs = tmp.alloc<SeqRec>((size_t)ntile * FR_SUBS_PER_TILE); Q.total = tmp.alloc<double>(1); Q.tsum = tmp.alloc<double>(ntile);
+    double *da = tmp.alloc<double>(n), *dout = tmp.alloc<double>(n);
     FR_HIP(hipMemcpy(da, vals, 8 * (size_t)n, hipMemcpyHostToDevice));
     FR_HIP(hipMemset(Q.subs, 0, sizeof(SeqRec) * (size_t)ntile * FR_SUBS_PER_TILE));
     AccArr acc{da, n};
-    double *dstart = fr_alloc<double>(1);
+    double *dstart = tmp.alloc<double>(1);
     FR_HIP(hipMemcpy(dstart, &start, 8, hipMemcpyHostToDevice));
     SeqStart from; from.norms = dstart; from.n = 1;      // 0 + start == start
     FR_LAUNCH(c, "k_seq_sums", (k_seq_sums<AccArr>), dim3(ntile), dim3(FR_BLOCK), Q, acc);
@@ -1384,7 +1330,6 @@ extern "C" int fries_test_seqsum(fries_ctx *h, const double *vals, uint32_t n, d
     for (unsigned t = 0; t < ntile; t++) if (tl[t].dirty) { dt++; for (int j = 0; j < FR_SUBS_PER_TILE; j++) if (sb[(size_t)t * FR_SUBS_PER_TILE + j].dirty) ds++; }
     if (n_dirty_tiles) *n_dirty_tiles = dt;
     if (n_dirty_subs) *n_dirty_subs = ds;
-    hipFree(Q.tiles); hipFree(Q.subs); hipFree(Q.total); hipFree(Q.tsum); hipFree(da); hipFree(dout); hipFree(dstart);
     FR_API_END
 }
 
@@ -1404,8 +1349,8 @@ extern "C" int fries_measure_copy_bandwidth(fries_ctx *h, size_t bytes, int reps
     FR_API_BEGIN
     FriesCtx *c = &h->c;
     FR_HIP(hipSetDevice(c->device));
-    void *a = nullptr, *b = nullptr;
-    FR_HIP(hipMalloc(&a, bytes)); FR_HIP(hipMalloc(&b, bytes));
+    DevMem tmp;
+    void *a = tmp.alloc<uint8_t>(bytes), *b = tmp.alloc<uint8_t>(bytes);
     FR_HIP(hipMemsetAsync(a, 1, bytes, c->stream));
     FR_HIP(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, c->stream));
     hipEvent_t e0, e1;
@@ -1417,7 +1362,7 @@ extern "C" int fries_measure_copy_bandwidth(fries_ctx *h, size_t bytes, int reps
     float ms = 0;
     FR_HIP(hipEventElapsedTime(&ms, e0, e1));
     *gb_per_s = 2.0 * (double)bytes * reps / (ms * 1e-3) / 1e9;
-    hipEventDestroy(e0); hipEventDestroy(e1); hipFree(a); hipFree(b);
+    hipEventDestroy(e0); hipEventDestroy(e1);
     FR_API_END
 }
 

@@ -536,35 +536,27 @@ void fr_fq_setup(FriesCtx *c, const fries_fciqmc_params *p) {
     if (p->max_dets == 0 || p->target_walkers == 0) throw FriesError("max_dets and target_walkers must be positive");
     c->fq = *p; c->fq_mode = true;
     c->eps = p->epsilon; c->target_norm = p->target_walkers; c->en_shift = 0; c->last_one_norm = 0; c->iterat = 0;
-    c->mt.seed(p->seed);
-    c->proc_scr.resize(2 * c->n_orb); c->vec_scr.resize(2 * c->n_orb);
-    if (c->in_proc_scr.size() == c->proc_scr.size()) c->proc_scr = c->in_proc_scr;     // --load_dir: load_proc_hash (fciqmc_mol.cpp:122-124)
-    else for (auto &x : c->proc_scr) x = c->mt();   // fciqmc_mol.cpp:126-128
-    for (auto &x : c->vec_scr) x = c->mt();         // :134-136
-    if (!c->comm.small_send) { c->own_small = fr_alloc<uint8_t>(2048); c->comm.small_send = c->own_small; }
     uint32_t spawn_length = p->target_walkers * 2;      // what a rank can spawn and receive; the reference's Adder holds
-    c->adder_cap = p->target_walkers / c->n_ranks / c->n_ranks * 2;      // target / n_procs^2 * 2 per destination (:107)
-    if (!c->d_proc_scr) c->d_proc_scr = fr_alloc<uint32_t>(64);
-    FR_HIP(hipMemcpyAsync(c->d_proc_scr, c->proc_scr.data(), 4 * c->proc_scr.size(), hipMemcpyHostToDevice, c->stream));
-    c->hf_proc = fr_host_idx_to_proc(c, c->hf_det);
-    fr_vec_alloc(c, &c->vec, p->max_dets);
-    fr_spawn_alloc(c, spawn_length + 4096);
-    fr_xch_alloc(c, spawn_length + 4096);
-    fr_vcomp_alloc(c, p->max_dets);                 // dots
+    // scramblers: fciqmc_mol.cpp:126-128, :134-136; --load_dir: load_proc_hash (:122-124).  Adder: target / n_procs^2 * 2 per destination (:107)
+    fr_driver_prologue(c, p->seed, true, false, p->target_walkers / c->n_ranks / c->n_ranks * 2);
+    fr_vec_alloc(c, c->mem, &c->vec, p->max_dets);
+    fr_spawn_alloc(c, c->mem, spawn_length + 4096);
+    fr_xch_alloc(c, c->mem, spawn_length + 4096);
+    fr_vcomp_alloc(c, c->mem, p->max_dets);                 // dots
     FqWork &Q = c->fqw;
     Q.cap_d = p->max_dets; Q.cap_a = spawn_length + 4096;
-    Q.n_doub = fr_alloc<uint32_t>(Q.cap_d); Q.n_att = fr_alloc<uint32_t>(Q.cap_d); Q.att_off = fr_alloc<uint32_t>(Q.cap_d); Q.new_val = fr_alloc<double>(Q.cap_d);
+    Q.n_doub = c->mem.alloc<uint32_t>(Q.cap_d); Q.n_att = c->mem.alloc<uint32_t>(Q.cap_d); Q.att_off = c->mem.alloc<uint32_t>(Q.cap_d); Q.new_val = c->mem.alloc<double>(Q.cap_d);
     unsigned nb = fr_blocks(Q.cap_d, FR_BLOCK) + 1, nba = fr_blocks(Q.cap_a, FR_BLOCK) + 1;
-    Q.blk_att = fr_alloc<uint32_t>(nb); Q.blk_nz = fr_alloc<uint32_t>(nb); Q.blk_ini = fr_alloc<uint32_t>(nb); Q.blk_sp = fr_alloc<uint32_t>(nba);
-    Q.totals = fr_alloc<uint32_t>(4); Q.norm = fr_alloc<double>(1); Q.heavy = fr_alloc<uint32_t>(Q.cap_d);
+    Q.blk_att = c->mem.alloc<uint32_t>(nb); Q.blk_nz = c->mem.alloc<uint32_t>(nb); Q.blk_ini = c->mem.alloc<uint32_t>(nb); Q.blk_sp = c->mem.alloc<uint32_t>(nba);
+    Q.totals = c->mem.alloc<uint32_t>(4); Q.norm = c->mem.alloc<double>(1); Q.heavy = c->mem.alloc<uint32_t>(Q.cap_d);
     FR_HIP(hipMemsetAsync(Q.totals, 0, 16, c->stream));
-    Q.sp_val = fr_alloc<double>(Q.cap_a); Q.sp_det = fr_alloc<det_t>(Q.cap_a); Q.sp_ini = fr_alloc<uint8_t>(Q.cap_a);
-    Q.o1cnt = p->heat_bath ? fr_alloc<uint32_t>((size_t)Q.cap_d * c->n_elec) : nullptr;
+    Q.sp_val = c->mem.alloc<double>(Q.cap_a); Q.sp_det = c->mem.alloc<det_t>(Q.cap_a); Q.sp_ini = c->mem.alloc<uint8_t>(Q.cap_a);
+    Q.o1cnt = p->heat_bath ? c->mem.alloc<uint32_t>((size_t)Q.cap_d * c->n_elec) : nullptr;
     Q.multi = 0; Q.n_walk = nullptr; Q.samp_unit = 1; Q.init_f = 0;
     if (p->real_walkers) {             // fciqmc_fp_mol
         if (c->use_comm && c->n_ranks > 1 && 2 * c->n_orb > 63) throw FriesError("fciqmc_fp_mol over ranks needs bit 63 of the index for the initiator flag (at most 31 orbitals)");
         c->dots_slot0_from_hf = true;      // fciqmc_fp_mol.cpp:461-462
-        Q.multi = 2; Q.n_walk = fr_alloc<uint32_t>(Q.cap_d);
+        Q.multi = 2; Q.n_walk = c->mem.alloc<uint32_t>(Q.cap_d);
     }
     if (p->heat_bath && (c->n_elec > 32 || c->n_orb - c->n_elec / 2 > 32)) throw FriesError("heat-bath sampling supports at most 32 electrons / 32 virtual orbitals per spin");
     fr_h_trial_setup(c);        // HF trial vector, H * trial, p_doub (:139-191, as in frisys_mol)
@@ -579,22 +571,11 @@ void fr_fq_setup(FriesCtx *c, const fries_fciqmc_params *p) {
         if (m >= c->adder_cap) throw FriesError("the initial vector fills the Adder (the reference would store the filling entry twice): raise --target");
         if (m) {
             std::vector<uint8_t> f(m, 1);
-            FR_HIP(hipMemcpyAsync(c->sp.det, d.data(), 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            FR_HIP(hipMemcpyAsync(c->sp.val, v.data(), 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            FR_HIP(hipMemcpyAsync(c->sp.ini, f.data(), m, hipMemcpyHostToDevice, c->stream));
-            FR_HIP(hipMemcpyAsync(c->sp.n_spawn, &m, 4, hipMemcpyHostToDevice, c->stream));
-            fr_vec_merge(c, &c->vec, m, true);
+            fr_spawn_upload_merge(c, d.data(), v.data(), f.data(), m, true);
             FR_HIP(hipStreamSynchronize(c->stream));
         }
     }
-    else if (c->rank == c->hf_proc) {                        // :239-243
-        double v = 100; uint8_t one = 1; uint32_t n1 = 1;
-        FR_HIP(hipMemcpyAsync(c->sp.det, &c->hf_det, 8, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.val, &v, 8, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.ini, &one, 1, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.n_spawn, &n1, 4, hipMemcpyHostToDevice, c->stream));
-        fr_vec_merge(c, &c->vec, 1, true);
-    }
+    else if (c->rank == c->hf_proc) fr_spawn_reference_det(c);     // :239-243
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
 }
 
@@ -650,7 +631,7 @@ void fr_fq_iterate(FriesCtx *c, fries_fciqmc_log *lg) {
             norm = 0;
             for (int q = 0; q < c->n_ranks; q++) norm += h[q];
         }
-        double damp = 0.05 / c->eps / 10;
+        double damp = 0.05 / c->eps / 10;        // (not fr_adjust_shift: fciqmc_mol.cpp divides in this order, here and below)
         if (c->last_one_norm) { c->en_shift -= damp * log(norm / c->last_one_norm); c->last_one_norm = norm; }
         if (c->last_one_norm == 0 && norm > c->target_norm) c->last_one_norm = norm;
     }
@@ -681,9 +662,7 @@ void fr_fq_iterate(FriesCtx *c, fries_fciqmc_log *lg) {
     if (lg) {
         lg->numer = c->numer; lg->denom = c->denom; lg->shift = c->en_shift; lg->norm = norm;
         lg->n_nonz = (int32_t)tot[1]; lg->n_ini = tot[2]; lg->curr_size = c->h_vst.curr_size; lg->n_spawn = n_spawn;
-        uint32_t e = 0;
-        FR_HIP(hipMemcpy(&e, c->d_err, 4, hipMemcpyDeviceToHost));
-        lg->err = e | c->h_vst.err; lg->n_attempts = A;
+        lg->err = fr_log_err(c); lg->n_attempts = A;
     }
 }
 
@@ -704,9 +683,9 @@ void fr_multi_setup(FriesCtx *c, const fries_frimulti_params *p) {
     c->target_norm = p->target_norm; c->init_thresh = p->initiator; c->vec_nonz = p->vec_nonz; c->mat_nonz = p->mat_nonz;
     c->adder_cap = p->mat_nonz * 2 / c->n_ranks / c->n_ranks;     // :89
     FqWork &Q = c->fqw;
-    Q.multi = 1; Q.n_walk = fr_alloc<uint32_t>(Q.cap_d); Q.init_f = p->initiator; Q.samp_unit = 1;
-    if (!c->W.kin) c->W.kin = fr_alloc<uint32_t>(p->max_dets);          // fr_sys_comp's tooth indices
-    if (!c->d_norms_keep) { c->d_norms_keep = fr_alloc<double>(FR_MAX_RANKS); c->d_seq_scratch = fr_alloc<double>(1); }
+    Q.multi = 1; Q.n_walk = c->mem.alloc<uint32_t>(Q.cap_d); Q.init_f = p->initiator; Q.samp_unit = 1;
+    if (!c->W.kin) c->W.kin = c->mem.alloc<uint32_t>(p->max_dets);          // fr_sys_comp's tooth indices
+    if (!c->d_norms_keep) { c->d_norms_keep = c->mem.alloc<double>(FR_MAX_RANKS); c->d_seq_scratch = c->mem.alloc<double>(1); }
     c->glob_norm = -1;                  // no compression yet: the first comb is spaced by the norm of the start vector (:227-233)
 }
 
@@ -760,11 +739,7 @@ void fr_multi_iterate(FriesCtx *c, fries_fciqmc_log *lg) {
     fr_find_preserve(c, &n_samp, &glob_norm);
     c->glob_norm = glob_norm;
     c->nkept = P.vec_nonz - n_samp;
-    if ((c->iterat + 1) % 10 == 0) {
-        double damp = 0.05 / 10 / c->eps;
-        if (c->last_one_norm) { c->en_shift -= damp * log(glob_norm / c->last_one_norm); c->last_one_norm = glob_norm; }
-        if (c->last_one_norm == 0 && glob_norm > c->target_norm) c->last_one_norm = glob_norm;
-    }
+    fr_adjust_shift(c, glob_norm);
     fr_dots(c, &c->numer, &c->denom);
     rn_sys = c->mt() / (1. + UINT32_MAX);
     fr_sys_comp(c, n_samp, rn_sys);        // incl. the deletes; the reference's HF test compares addresses (:417), so HF goes like any other
@@ -774,8 +749,6 @@ void fr_multi_iterate(FriesCtx *c, fries_fciqmc_log *lg) {
         fr_vec_sync_state(c, &c->vec, &c->h_vst);
         lg->numer = c->numer; lg->denom = c->denom; lg->shift = c->en_shift; lg->norm = glob_norm;
         lg->n_nonz = c->h_vst.n_nonz; lg->n_ini = tot[2]; lg->curr_size = c->h_vst.curr_size; lg->n_spawn = n_spawn;
-        uint32_t e = 0;
-        FR_HIP(hipMemcpy(&e, c->d_err, 4, hipMemcpyDeviceToHost));
-        lg->err = e | c->h_vst.err; lg->n_attempts = A;
+        lg->err = fr_log_err(c); lg->n_attempts = A;
     }
 }

@@ -314,92 +314,91 @@ static void fr_sys_timing_dump(FriesCtx *c, const char *name, int stage, unsigne
     FR_HIP(hipMemset(c->W.tdbg, 0, h.size() * 8));
 }
 #endif
-void fr_hbpp_alloc(FriesCtx *c, uint32_t cap) {
+void fr_hbpp_alloc(FriesCtx *c, DevMem &m, uint32_t cap) {
     CompWork &W = c->W;
     W.cap = cap;
     for (int h = 0; h < 2; h++) {
-        W.el[h].val = fr_alloc<double>(cap); W.el[h].pos = fr_alloc<uint32_t>(cap); W.el[h].code = fr_alloc<uint32_t>(cap);
-        W.el[h].ndiv = fr_alloc<uint32_t>(cap); W.el[h].nsub = fr_alloc<uint32_t>(cap);
-        W.el[h].rinv = fr_alloc<double>(cap); W.el[h].raux = fr_alloc<uint32_t>(cap); W.el[h].det = fr_alloc<det_t>(cap);
-        W.psum[h] = fr_alloc<double>(FR_MAX_PART); W.pcnt[h] = fr_alloc<uint32_t>(FR_MAX_PART);
+        W.el[h].val = m.alloc<double>(cap); W.el[h].pos = m.alloc<uint32_t>(cap); W.el[h].code = m.alloc<uint32_t>(cap);
+        W.el[h].ndiv = m.alloc<uint32_t>(cap); W.el[h].nsub = m.alloc<uint32_t>(cap);
+        W.el[h].rinv = m.alloc<double>(cap); W.el[h].raux = m.alloc<uint32_t>(cap); W.el[h].det = m.alloc<det_t>(cap);
+        W.psum[h] = m.alloc<double>(FR_MAX_PART); W.pcnt[h] = m.alloc<uint32_t>(FR_MAX_PART);
     }
-    W.wt_remain = fr_alloc<double>(cap); W.keep = fr_alloc<uint32_t>(cap); W.S = fr_alloc<double>(cap);
-    W.kin = fr_alloc<uint32_t>(cap); W.cnt = fr_alloc<uint32_t>(cap);
+    W.wt_remain = m.alloc<double>(cap); W.keep = m.alloc<uint32_t>(cap); W.S = m.alloc<double>(cap);
+    W.kin = m.alloc<uint32_t>(cap); W.cnt = m.alloc<uint32_t>(cap);
     W.kend = nullptr; W.act[0] = W.act[1] = nullptr; W.act_n = nullptr; W.kstart = nullptr; W.prop = 0;
-    W.e_wi = fr_alloc<uint32_t>(cap); W.e_sub = fr_alloc<uint32_t>(cap); W.e_val = fr_alloc<double>(cap);
-    W.state = fr_alloc<CompState>(FR_MAX_ROUNDS + 2);
+    W.e_wi = m.alloc<uint32_t>(cap); W.e_sub = m.alloc<uint32_t>(cap); W.e_val = m.alloc<double>(cap);
+    W.state = m.alloc<CompState>(FR_MAX_ROUNDS + 2);
     W.stg = nullptr; W.spill = nullptr; W.spill_cnt = nullptr; W.tile_dirty = nullptr;
     if (!(getenv("FRIES_NO_STAGING") && atoi(getenv("FRIES_NO_STAGING")))) {       // emissions staged by k_sys_count (comp_kernels.hpp); FRIES_NO_STAGING=1: k_sys_write evaluates the rows again
         const size_t ntile = fr_blocks(cap, FR_TILE) + 1;
-        c->stg_mem = fr_alloc<uint4>(ntile * FR_BLOCK * FR_STG_SLOTS); c->spill_mem = fr_alloc<uint4>(ntile * FR_STG_SPILL);
-        c->spill_cnt_mem = fr_alloc<uint32_t>(ntile); c->tile_dirty_mem = fr_alloc<uint8_t>(ntile);
+        c->stg_mem = m.alloc<uint4>(ntile * FR_BLOCK * FR_STG_SLOTS); c->spill_mem = m.alloc<uint4>(ntile * FR_STG_SPILL);
+        c->spill_cnt_mem = m.alloc<uint32_t>(ntile); c->tile_dirty_mem = m.alloc<uint8_t>(ntile);
     }
-    W.teeth = fr_alloc<Teeth>(1);
-    W.fix_list = fr_alloc<uint32_t>(FR_MAX_FIX);
-    W.seq.tiles = fr_alloc<SeqRec>(FR_MAX_PART); W.seq.subs = fr_alloc<SeqRec>((size_t)FR_MAX_PART * FR_SUBS_PER_TILE); W.seq.total = fr_alloc<double>(1); W.seq.tsum = fr_alloc<double>(FR_MAX_PART);
+    W.teeth = m.alloc<Teeth>(1);
+    W.fix_list = m.alloc<uint32_t>(FR_MAX_FIX);
+    W.seq.tiles = m.alloc<SeqRec>(FR_MAX_PART); W.seq.subs = m.alloc<SeqRec>((size_t)FR_MAX_PART * FR_SUBS_PER_TILE); W.seq.total = m.alloc<double>(1); W.seq.tsum = m.alloc<double>(FR_MAX_PART);
 #ifdef FR_SEQ_TIMING
     W.seq.dbg = getenv("FRIES_SEQ_DBG") ? 1 : 0;
 #endif
 #ifdef FR_SYS_TIMING
-    W.tdbg = getenv("FRIES_SYS_DBG") ? fr_alloc<unsigned long long>(8192 * 8) : nullptr;
+    W.tdbg = getenv("FRIES_SYS_DBG") ? m.alloc<unsigned long long>(8192 * 8) : nullptr;
 #endif
     {
         Fks2Work &F = c->F2;
         F.nb8_cap = (uint32_t)(((size_t)cap / 8 + 2 + FR_FKS_CHUNK - 1) / FR_FKS_CHUNK * FR_FKS_CHUNK);     // whole chunks: k_fks_scan uses unguarded vector loads
         size_t n8 = (size_t)FR_FKS_PMAX * F.nb8_cap;
-        F.dk8 = fr_alloc<uint32_t>(n8); F.dg8 = fr_alloc<double>(n8); F.ws8 = fr_alloc<double>(n8);
-        F.cdirty = fr_alloc<uint32_t>(FR_FKS_MAXCHUNK);
+        F.dk8 = m.alloc<uint32_t>(n8); F.dg8 = m.alloc<double>(n8); F.ws8 = m.alloc<double>(n8);
+        F.cdirty = m.alloc<uint32_t>(FR_FKS_MAXCHUNK);
         {   // the replay loop's readback block: pinned, host-coherent, mapped into the device's address space
-            void *hp = nullptr, *dp = nullptr;
-            FR_HIP(hipHostMalloc(&hp, sizeof(FksHost), hipHostMallocMapped | hipHostMallocCoherent));
+            void *hp = m.alloc_pinned<FksHost>(1, true), *dp = nullptr;
             for (size_t q = 0; q < sizeof(FksHost); q++) ((volatile uint8_t *)hp)[q] = 0;
             FR_HIP(hipHostGetDevicePointer(&dp, hp, 0));
             c->h_fks = (FksHost *)hp; F.hm = (FksHost *)dp;
         }
         F.nwv_cap = F.nb8_cap / 8;
         const size_t nw = (size_t)FR_FKS_PMAX * F.nwv_cap;
-        F.wrec = fr_alloc<FksWRec>(nw); F.wNp = fr_alloc<uint32_t>(F.nwv_cap);
+        F.wrec = m.alloc<FksWRec>(nw); F.wNp = m.alloc<uint32_t>(F.nwv_cap);
         FR_HIP(hipMemset(F.wNp, 0xff, 4 * (size_t)F.nwv_cap));
-        F.xk8 = fr_alloc<uint32_t>(n8); F.xg8 = fr_alloc<double>(n8);
-        F.scal = fr_alloc<FksScal>(1); F.hist = fr_alloc<uint32_t>(FR_MAX_ROUNDS + 2);
-        F.ck = fr_alloc<uint32_t>((size_t)FR_FKS_PMAX * FR_FKS_MAXCHUNK); F.cg = fr_alloc<double>((size_t)FR_FKS_PMAX * FR_FKS_MAXCHUNK); F.cw = fr_alloc<double>((size_t)FR_FKS_PMAX * FR_FKS_MAXCHUNK);
-        F.ckx = fr_alloc<uint32_t>((size_t)FR_FKS_PMAX * FR_FKS_MAXCHUNK); F.cgx = fr_alloc<double>((size_t)FR_FKS_PMAX * FR_FKS_MAXCHUNK);
-        c->fks_wkx = fr_alloc<uint32_t>((size_t)8 * FR_FKS_PMAX * FR_FKS_MAXCHUNK); c->fks_wgx = fr_alloc<double>((size_t)8 * FR_FKS_PMAX * FR_FKS_MAXCHUNK);
+        F.xk8 = m.alloc<uint32_t>(n8); F.xg8 = m.alloc<double>(n8);
+        F.scal = m.alloc<FksScal>(1); F.hist = m.alloc<uint32_t>(FR_MAX_ROUNDS + 2);
+        F.ck = m.alloc<uint32_t>((size_t)FR_FKS_PMAX * FR_FKS_MAXCHUNK); F.cg = m.alloc<double>((size_t)FR_FKS_PMAX * FR_FKS_MAXCHUNK); F.cw = m.alloc<double>((size_t)FR_FKS_PMAX * FR_FKS_MAXCHUNK);
+        F.ckx = m.alloc<uint32_t>((size_t)FR_FKS_PMAX * FR_FKS_MAXCHUNK); F.cgx = m.alloc<double>((size_t)FR_FKS_PMAX * FR_FKS_MAXCHUNK);
+        c->fks_wkx = m.alloc<uint32_t>((size_t)8 * FR_FKS_PMAX * FR_FKS_MAXCHUNK); c->fks_wgx = m.alloc<double>((size_t)8 * FR_FKS_PMAX * FR_FKS_MAXCHUNK);
         FR_HIP(hipMemset(F.hist, 0, 4 * (FR_MAX_ROUNDS + 2)));
-        F.dbg_cnt = fr_alloc<uint32_t>((size_t)FR_MAX_ROUNDS * 4);
+        F.dbg_cnt = m.alloc<uint32_t>((size_t)FR_MAX_ROUNDS * 4);
         FR_HIP(hipMemset(F.dbg_cnt, 0, (size_t)FR_MAX_ROUNDS * 16));
-        c->fks_sxk8 = fr_alloc<uint32_t>((size_t)6 * FR_FKS_SROWS * F.nb8_cap); c->fks_sxg8 = fr_alloc<double>((size_t)6 * FR_FKS_SROWS * F.nb8_cap);
-        c->fks_saved = fr_alloc<FksSaved>(8);
+        c->fks_sxk8 = m.alloc<uint32_t>((size_t)6 * FR_FKS_SROWS * F.nb8_cap); c->fks_sxg8 = m.alloc<double>((size_t)6 * FR_FKS_SROWS * F.nb8_cap);
+        c->fks_saved = m.alloc<FksSaved>(8);
         FR_HIP(hipMemset(c->fks_saved, 0, 8 * sizeof(FksSaved)));
         {
             const float ex = getenv("FRIES_FKS_WARM_EXTRAP") ? (float)atof(getenv("FRIES_FKS_WARM_EXTRAP")) : FR_FKS_WARM_EXTRAP;
             if (ex > 0.0f) { FksSaved hsv{}; hsv.extrap = ex; for (int k = 0; k < 8; k++) FR_HIP(hipMemcpy(c->fks_saved + k, &hsv, sizeof(FksSaved), hipMemcpyHostToDevice)); }
         }
-        c->fks_wk = fr_alloc<uint32_t>((size_t)8 * FR_FKS_PMAX * FR_FKS_MAXCHUNK); c->fks_wg = fr_alloc<double>((size_t)8 * FR_FKS_PMAX * FR_FKS_MAXCHUNK);
+        c->fks_wk = m.alloc<uint32_t>((size_t)8 * FR_FKS_PMAX * FR_FKS_MAXCHUNK); c->fks_wg = m.alloc<double>((size_t)8 * FR_FKS_PMAX * FR_FKS_MAXCHUNK);
         FR_HIP(hipMemset(F.scal, 0, sizeof(FksScal)));
     }
-    c->d_norms_keep = fr_alloc<double>(FR_MAX_RANKS); c->d_seq_scratch = fr_alloc<double>(1); c->d_norms_all = fr_alloc<double>(FR_MAX_RANKS);
-    c->fks_seq = fr_alloc<FksSeq>(1);
+    c->d_norms_keep = m.alloc<double>(FR_MAX_RANKS); c->d_seq_scratch = m.alloc<double>(1); c->d_norms_all = m.alloc<double>(FR_MAX_RANKS);
+    c->fks_seq = m.alloc<FksSeq>(1);
     {   // work arrays of the parallel form of the in-order sweep (fks_seq.hpp)
         FksSq &SQ = c->fsq;
         const size_t nt = fr_blocks(cap, FR_SQ_TILE) + 1, ne = nt * FR_SQ_TILE, nb = nt * 32;
-        SQ.dl = fr_alloc<double>(ne); SQ.nwr = fr_alloc<double>(ne); SQ.nkp = fr_alloc<uint32_t>(ne);
-        SQ.gb = fr_alloc<double>(nb); SQ.lb = fr_alloc<double>(nb); SQ.dgb = fr_alloc<double>(nb); SQ.kb = fr_alloc<uint32_t>(nb); SQ.dk = fr_alloc<uint32_t>(nb);
-        SQ.tk = fr_alloc<uint32_t>(nt); SQ.tkx = fr_alloc<uint32_t>(nt); SQ.tg = fr_alloc<double>(nt); SQ.tgx = fr_alloc<double>(nt); SQ.tany = fr_alloc<uint8_t>(nt);
-        SQ.ctl = fr_alloc<FksSqCtl>(1);
+        SQ.dl = m.alloc<double>(ne); SQ.nwr = m.alloc<double>(ne); SQ.nkp = m.alloc<uint32_t>(ne);
+        SQ.gb = m.alloc<double>(nb); SQ.lb = m.alloc<double>(nb); SQ.dgb = m.alloc<double>(nb); SQ.kb = m.alloc<uint32_t>(nb); SQ.dk = m.alloc<uint32_t>(nb);
+        SQ.tk = m.alloc<uint32_t>(nt); SQ.tkx = m.alloc<uint32_t>(nt); SQ.tg = m.alloc<double>(nt); SQ.tgx = m.alloc<double>(nt); SQ.tany = m.alloc<uint8_t>(nt);
+        SQ.ctl = m.alloc<FksSqCtl>(1);
         FR_HIP(hipMemset(SQ.ctl, 0, sizeof(FksSqCtl)));
-        SQ.mG = fr_alloc<double>(nt); SQ.mL = fr_alloc<double>(nt); SQ.sabs = fr_alloc<double>(nt); SQ.gt = fr_alloc<double>(nt); SQ.lt = fr_alloc<double>(nt);
-        SQ.eG = fr_alloc<int32_t>(nt); SQ.eL = fr_alloc<int32_t>(nt); SQ.mflag = fr_alloc<uint8_t>(nt); SQ.fast = fr_alloc<uint8_t>(nt);
+        SQ.mG = m.alloc<double>(nt); SQ.mL = m.alloc<double>(nt); SQ.sabs = m.alloc<double>(nt); SQ.gt = m.alloc<double>(nt); SQ.lt = m.alloc<double>(nt);
+        SQ.eG = m.alloc<int32_t>(nt); SQ.eL = m.alloc<int32_t>(nt); SQ.mflag = m.alloc<uint8_t>(nt); SQ.fast = m.alloc<uint8_t>(nt);
         c->fsq_check = getenv("FRIES_FSQ_CHECK") && atoi(getenv("FRIES_FSQ_CHECK"));
         if (getenv("FRIES_FSQ_MAPS")) c->fsq_use_maps = atoi(getenv("FRIES_FSQ_MAPS")) != 0;
-        SQ.gb2 = c->fsq_check ? fr_alloc<double>(nb) : nullptr; SQ.lb2 = c->fsq_check ? fr_alloc<double>(nb) : nullptr;
+        SQ.gb2 = c->fsq_check ? m.alloc<double>(nb) : nullptr; SQ.lb2 = c->fsq_check ? m.alloc<double>(nb) : nullptr;
         c->fsq_walk_only = getenv("FRIES_FKS_SEQ_WALK") && atoi(getenv("FRIES_FKS_SEQ_WALK"));
         if (getenv("FRIES_FSQ_GUESS_ROUNDS")) c->fsq_guess_rounds = atoi(getenv("FRIES_FSQ_GUESS_ROUNDS"));
         if (getenv("FRIES_FSQ_EXACT_ROUNDS")) c->fsq_exact_rounds = atoi(getenv("FRIES_FSQ_EXACT_ROUNDS"));
         if (getenv("FRIES_FSQ_SPARSE_MAX")) c->fsq_sparse_max = atoi(getenv("FRIES_FSQ_SPARSE_MAX"));
     }
-    c->c_pos = fr_alloc<uint32_t>(cap); c->c_orbs = fr_alloc<uint32_t>(cap); c->c_val = fr_alloc<double>(cap);
-    c->d_nsucc = fr_alloc<uint32_t>(1);
+    c->c_pos = m.alloc<uint32_t>(cap); c->c_orbs = m.alloc<uint32_t>(cap); c->c_val = m.alloc<double>(cap);
+    c->d_nsucc = m.alloc<uint32_t>(1);
     FR_HIP(hipMemset(W.state, 0, sizeof(CompState) * (FR_MAX_ROUNDS + 2)));
     if (fr_blocks(cap, FR_TILE) > FR_MAX_PART) throw FriesError("work capacity exceeds FR_MAX_PART tiles");
 }
@@ -795,7 +794,7 @@ static void run_stage(FriesCtx *c, int cur, uint32_t n_bound, uint32_t n_samp, d
         else FR_LAUNCH(c, "k_sys_fixup", (k_sys_fixup<STAGE, NEW_HB>), dim3(1), dim3(FR_BLOCK), W, c->vec, c->d_hb, cur, c->p_doub, c->d_err);
     }
     // the stage's emission count also goes to the host block (word 16 + slot): a copy into pageable memory would hold the host until it is done
-    fr_rb_init(c);
+    fr_rb_init(c, c->mem);
     FR_LAUNCH(c, "k_sys_write", (k_sys_write<STAGE, NEW_HB>), dim3(grid), dim3(FR_BLOCK), W, c->vec, c->d_hb, cur, c->p_doub, c->d_err, out_slot >= 0 ? c->d_misc() + 16 + out_slot : nullptr);
 #ifdef FR_SYS_TIMING
     fr_sys_timing_dump(c, "k_sys_write", STAGE, grid, 5);
@@ -1096,7 +1095,7 @@ static uint32_t pv_stage(FriesCtx *c, int cur, uint32_t n_in, uint32_t n_samp) {
         if (c->use_comm) fr_piv_comp_flat(c, 0, n_samp);     // the other ranks' compression still needs this one in its collectives
         return 0;
     }
-    if (n_long > F.cap) fr_piv_flat_reserve(c, n_long + n_long / 4 + 1024);
+    if (n_long > F.cap) fr_piv_flat_reserve(c, c->mem, n_long + n_long / 4 + 1024);
     PvLong L{F.vals, F.parent, c->pv_goff, F.vc.del, F.total};
     FR_LAUNCH(c, "k_pv_expand", (k_pv_expand<STAGE, NEW_HB>), dim3(grid), dim3(FR_BLOCK), W, c->vec, c->d_hb, cur, c->p_doub, W.pcnt[0], L);
     fr_piv_comp_flat(c, n_long, n_samp);
@@ -1118,8 +1117,8 @@ static void hbpp_piv_t(FriesCtx *c, uint32_t n_samp, int unit_matrel, uint32_t s
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     uint32_t n = c->h_vst.curr_size;
     if (n > W.cap) throw FriesError("vector larger than HB-PP work capacity");
-    if (!c->pv_goff) c->pv_goff = fr_alloc<uint32_t>(W.cap);
-    fr_piv_flat_reserve(c, 2 * (n > n_samp ? n : n_samp) + 1024);
+    if (!c->pv_goff) c->pv_goff = c->mem.alloc<uint32_t>(W.cap);
+    fr_piv_flat_reserve(c, c->mem, 2 * (n > n_samp ? n : n_samp) + 1024);
     n = pv_stage<1, NEW_HB>(c, 0, n, n_samp); stage_len[0] = n;
     n = pv_stage<2, NEW_HB>(c, 1, n, n_samp); stage_len[1] = n;
     n = pv_stage<3, NEW_HB>(c, 0, n, n_samp); stage_len[2] = n;

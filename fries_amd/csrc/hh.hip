@@ -284,50 +284,36 @@ void fr_hh_setup(FriesCtx *c, const fries_hh_params *p) {
     c->eps = p->eps; c->target_norm = p->target_norm; c->init_thresh = p->initiator;
     c->vec_nonz = p->vec_nonz; c->mat_nonz = p->vec_nonz;
     c->en_shift = 0; c->last_one_norm = 0; c->iterat = 0;
-    c->mt.seed(p->seed);
     const unsigned L = p->n_sites;
-    c->proc_scr.resize(2 * L); c->vec_scr.resize(2 * L);
-    // frisys_hh.cpp:80-83, :88-91; a caller that drew them itself (the reference's driver behind include/FRIES) hands them in
-    if (c->in_proc_scr.size() == c->proc_scr.size()) c->proc_scr = c->in_proc_scr; else for (auto &x : c->proc_scr) x = c->mt();
-    if (c->in_vec_scr.size() == c->vec_scr.size()) c->vec_scr = c->in_vec_scr; else for (auto &x : c->vec_scr) x = c->mt();
-    uint32_t wcap = p->max_dets > p->vec_nonz + 4096 ? p->max_dets : p->vec_nonz + 4096;
-    if (!c->comm.small_send) { c->own_small = fr_alloc<uint8_t>(2048); c->comm.small_send = c->own_small; }
-    if (!c->d_proc_scr) c->d_proc_scr = fr_alloc<uint32_t>(64);
-    if (!c->d_vec_scr) c->d_vec_scr = fr_alloc<uint32_t>(64);
-    FR_HIP(hipMemcpyAsync(c->d_proc_scr, c->proc_scr.data(), 4 * c->proc_scr.size(), hipMemcpyHostToDevice, c->stream));
-    FR_HIP(hipMemcpyAsync(c->d_vec_scr, c->vec_scr.data(), 4 * c->vec_scr.size(), hipMemcpyHostToDevice, c->stream));
-    if (!c->d_hb) { c->d_hb = fr_alloc<HbTables>(1); FR_HIP(hipMemsetAsync(c->d_hb, 0, sizeof(HbTables), c->stream)); }     // unused by uniform stages, but staged
-    c->adder_cap = (uint32_t)((uint64_t)p->vec_nonz * 4 / c->n_ranks);      // the Adder gets spawn_length here (:94, :100)
-    if (p->full) { uint64_t sl = (uint64_t)p->n_elec * 4 * p->max_dets / c->n_ranks; c->adder_cap = sl > 200000 ? 200000u : (uint32_t)sl; }      // frifull_hh.cpp:91-95
-    fr_vec_alloc(c, &c->vec, p->max_dets);
-    c->vec.hh_sites = L; c->vec.hh_nelec = p->n_elec; c->vec.hh_buckets = p->max_dets; c->vec.hh_scr = c->d_vec_scr;
-    fr_hbpp_alloc(c, wcap);
-    // un-normalised stage-1 rows make comb repairs the rule rather than the exception (comp_kernels.hpp: k_sys_prop)
-    c->W.prop = 1; c->W.kend = fr_alloc<uint32_t>(wcap); c->W.act[0] = fr_alloc<uint32_t>(wcap + 1); c->W.act[1] = fr_alloc<uint32_t>(wcap + 1); c->W.act_n = fr_alloc<uint32_t>(2);
-    c->W.kstart = fr_alloc<uint32_t>(wcap + 1); FR_HIP(hipMemset(c->W.kstart, 0, 4 * ((size_t)wcap + 1)));
-    // frifull_hh: at most 4 n_elec adds per stored state (2 hops and 2 phonon moves per electron), vec_nonz states after a compression
-    const uint64_t sp_need = p->full ? (uint64_t)4 * p->n_elec * ((uint64_t)p->vec_nonz + 64) + 4096 : (uint64_t)p->vec_nonz + 4096;
-    if (sp_need > 0x7fffffffull) throw FriesError("vec_nonz too large for the spawn list");
-    fr_spawn_alloc(c, (uint32_t)sp_need);
-    fr_xch_alloc(c, (uint32_t)sp_need);
-    if (p->full) c->hhf_cnt = fr_alloc<unsigned long long>(2);
-    fr_vcomp_alloc(c, p->max_dets);
-    c->hh_fdet = fr_alloc<det_t>(wcap);
-    c->hh_ovlp = fr_alloc<double>(4 + FR_HH_OVLP_BLOCKS);
-    c->W.row1[0] = 1.0; c->W.row1[1] = p->g;        // {hub_t, elec_ph}, :191-192
     // Neel state: alpha electrons on the even sites, beta on the odd ones (hub_holstein.cpp:139-171)
     det_t neel = 0;
     for (unsigned k = 0; k < p->n_elec / 2; k++) { neel |= 1ull << (2 * k); neel |= 1ull << (L + 2 * k + 1); }
     c->hf_det = neel;
-    c->hf_proc = fr_host_idx_to_proc(c, neel);
-    if (c->rank == c->hf_proc) {
-        double v = 100; uint8_t one = 1; uint32_t n1 = 1;
-        FR_HIP(hipMemcpyAsync(c->sp.det, &c->hf_det, 8, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.val, &v, 8, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.ini, &one, 1, hipMemcpyHostToDevice, c->stream));
-        FR_HIP(hipMemcpyAsync(c->sp.n_spawn, &n1, 4, hipMemcpyHostToDevice, c->stream));
-        fr_vec_merge(c, &c->vec, 1, true);
-    }
+    uint32_t adder_cap = (uint32_t)((uint64_t)p->vec_nonz * 4 / c->n_ranks);      // the Adder gets spawn_length here (:94, :100)
+    if (p->full) { uint64_t sl = (uint64_t)p->n_elec * 4 * p->max_dets / c->n_ranks; adder_cap = sl > 200000 ? 200000u : (uint32_t)sl; }      // frifull_hh.cpp:91-95
+    // scramblers over 2 L entries (frisys_hh.cpp:80-83, :88-91); a caller that drew them itself (the reference's driver behind include/FRIES) hands them in
+    fr_driver_prologue(c, p->seed, true, true, adder_cap);
+    uint32_t wcap = p->max_dets > p->vec_nonz + 4096 ? p->max_dets : p->vec_nonz + 4096;
+    if (!c->d_vec_scr) c->d_vec_scr = c->mem.alloc<uint32_t>(64);        // this driver's vector hash is keyed on the device, too
+    FR_HIP(hipMemcpyAsync(c->d_vec_scr, c->vec_scr.data(), 4 * c->vec_scr.size(), hipMemcpyHostToDevice, c->stream));
+    if (!c->d_hb) { c->d_hb = c->mem.alloc<HbTables>(1); FR_HIP(hipMemsetAsync(c->d_hb, 0, sizeof(HbTables), c->stream)); }     // unused by uniform stages, but staged
+    fr_vec_alloc(c, c->mem, &c->vec, p->max_dets);
+    c->vec.hh_sites = L; c->vec.hh_nelec = p->n_elec; c->vec.hh_buckets = p->max_dets; c->vec.hh_scr = c->d_vec_scr;
+    fr_hbpp_alloc(c, c->mem, wcap);
+    // un-normalised stage-1 rows make comb repairs the rule rather than the exception (comp_kernels.hpp: k_sys_prop)
+    c->W.prop = 1; c->W.kend = c->mem.alloc<uint32_t>(wcap); c->W.act[0] = c->mem.alloc<uint32_t>(wcap + 1); c->W.act[1] = c->mem.alloc<uint32_t>(wcap + 1); c->W.act_n = c->mem.alloc<uint32_t>(2);
+    c->W.kstart = c->mem.alloc<uint32_t>(wcap + 1); FR_HIP(hipMemset(c->W.kstart, 0, 4 * ((size_t)wcap + 1)));
+    // frifull_hh: at most 4 n_elec adds per stored state (2 hops and 2 phonon moves per electron), vec_nonz states after a compression
+    const uint64_t sp_need = p->full ? (uint64_t)4 * p->n_elec * ((uint64_t)p->vec_nonz + 64) + 4096 : (uint64_t)p->vec_nonz + 4096;
+    if (sp_need > 0x7fffffffull) throw FriesError("vec_nonz too large for the spawn list");
+    fr_spawn_alloc(c, c->mem, (uint32_t)sp_need);
+    fr_xch_alloc(c, c->mem, (uint32_t)sp_need);
+    if (p->full) c->hhf_cnt = c->mem.alloc<unsigned long long>(2);
+    fr_vcomp_alloc(c, c->mem, p->max_dets);
+    c->hh_fdet = c->mem.alloc<det_t>(wcap);
+    c->hh_ovlp = c->mem.alloc<double>(4 + FR_HH_OVLP_BLOCKS);
+    c->W.row1[0] = 1.0; c->W.row1[1] = p->g;        // {hub_t, elec_ph}, :191-192
+    if (c->rank == c->hf_proc) fr_spawn_reference_det(c);       // 100 x Neel
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
 }
 
@@ -393,11 +379,7 @@ void fr_hh_iterate(FriesCtx *c, fries_iter_log *lg) {
     fr_find_preserve(c, &n_samp, &glob_norm);
     c->glob_norm = glob_norm;
     c->nkept = c->vec_nonz - n_samp;
-    if ((c->iterat + 1) % 10 == 0) {
-        double damp = 0.05 / 10 / c->eps;
-        if (c->last_one_norm) { c->en_shift -= damp * log(glob_norm / c->last_one_norm); c->last_one_norm = glob_norm; }
-        if (c->last_one_norm == 0 && glob_norm > c->target_norm) c->last_one_norm = glob_norm;
-    }
+    fr_adjust_shift(c, glob_norm);
     // energy estimate (:336-349): every shard's overlap with the Neel state, gathered to the rank that owns it
     FR_LAUNCH(c, "k_hh_ref_ovlp", k_hh_ref_ovlp, dim3(FR_HH_OVLP_BLOCKS), dim3(FR_BLOCK), c->vec, c->hf_det, P.g / 1.0, c->hh_ovlp + 4);
     FR_LAUNCH(c, "k_hh_ref_ovlp_sum", k_hh_ref_ovlp_sum, dim3(1), dim3(64), c->vec, c->hh_ovlp + 4, c->hh_ovlp);
@@ -430,9 +412,7 @@ void fr_hh_iterate(FriesCtx *c, fries_iter_log *lg) {
         lg->nkept = c->nkept; lg->n_nonz = c->h_vst.n_nonz; lg->curr_size = c->h_vst.curr_size;
         lg->num_success = c->num_success;
         for (int k = 0; k < 5; k++) lg->comp_len[k] = k < 2 ? c->comp_len[k] : 0;
-        uint32_t e = 0;
-        FR_HIP(hipMemcpy(&e, c->d_err, 4, hipMemcpyDeviceToHost));
-        lg->err = e | c->h_vst.err;
+        lg->err = fr_log_err(c);
     }
 }
 

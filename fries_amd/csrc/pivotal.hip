@@ -12,13 +12,13 @@
 #include "ctx.hpp"
 
 struct DD_host { double hi, lo; };
-static void piv_alloc(FriesCtx *c, PivBuf &P, uint32_t cap) {
+static void piv_alloc(DevMem &m, PivBuf &P, uint32_t cap) {
     if (P.cap >= cap) return;
-    if (P.start) { FR_HIP(hipFree(P.start)); FR_HIP(hipFree(P.carry)); FR_HIP(hipFree(P.U)); FR_HIP(hipFree(P.unit)); FR_HIP(hipFree(P.scal)); FR_HIP(hipFree(P.nz_start)); }
-    P.start = fr_alloc<uint32_t>(cap); P.carry = fr_alloc<double>(cap); P.U = fr_alloc<double>(2 * (size_t)cap); P.unit = fr_alloc<PivUnit>(cap);
-    P.nz_start = fr_alloc<uint32_t>(cap);
-    P.scal = fr_alloc<PivScal>(1);
-    if (!P.tile_dd) { P.tile_dd = fr_alloc<DD_host>(FR_MAX_PART); P.tile_nz = fr_alloc<uint32_t>(FR_MAX_PART); }
+    m.release(P.start); m.release(P.carry); m.release(P.U); m.release(P.unit); m.release(P.scal); m.release(P.nz_start);
+    P.start = m.alloc<uint32_t>(cap); P.carry = m.alloc<double>(cap); P.U = m.alloc<double>(2 * (size_t)cap); P.unit = m.alloc<PivUnit>(cap);
+    P.nz_start = m.alloc<uint32_t>(cap);
+    P.scal = m.alloc<PivScal>(1);
+    if (!P.tile_dd) { P.tile_dd = m.alloc<DD_host>(FR_MAX_PART); P.tile_nz = m.alloc<uint32_t>(FR_MAX_PART); }
     P.cap = cap;
 }
 
@@ -510,7 +510,7 @@ static void piv_comp_core(FriesCtx *c, uint32_t compress_size, uint32_t *n_kept,
     if (n_kept) *n_kept = compress_size - n_samp;
     if (glob_norm_out) *glob_norm_out = gn;
     PivBuf &P = c->piv;       // created on first use
-    piv_alloc(c, P, c->vec.cap);
+    piv_alloc(c->mem, P, c->vec.cap);
     FR_HIP(hipMemsetAsync(P.scal, 0, sizeof(PivScal), st));
     double mine = 0;
     if (n_samp) {
@@ -603,40 +603,26 @@ void fr_piv_comp(FriesCtx *c, uint32_t compress_size, uint32_t *n_kept, double *
 // piv_comp_parallel (compress_utils.cpp:354-386) of a plain device array of n values (apply_HBPP_piv's long_vec): afterwards
 // F.vals holds the compressed values and F.vc.del[i] == 1 marks the elements that ended up zero.  The array rides through the same
 // kernels as the solution vector: for the duration of the call it IS c->vec (a VecDev whose only live members are v0 and st).
-void fr_piv_flat_reserve(FriesCtx *c, uint32_t cap) {
+void fr_piv_flat_reserve(FriesCtx *c, DevMem &m, uint32_t cap) {
     FlatPiv &F = c->flat;
     if (F.cap >= cap) return;
     if (fr_blocks(cap, FR_TILE) > FR_MAX_PART) throw FriesError("pivotal matrix compression: a factor expands to more elements than the work arrays index (134e6)");
     if (F.cap) {
         FR_HIP(hipStreamSynchronize(c->stream));
-        FR_HIP(hipFree(F.vals)); FR_HIP(hipFree(F.parent));
+        m.release(F.vals); m.release(F.parent);
         VcompBuf &B = F.vc;
-        FR_HIP(hipFree(B.keep)); FR_HIP(hipFree(B.del)); FR_HIP(hipFree(B.S));
-        for (int h = 0; h < 2; h++) { FR_HIP(hipFree(B.psum[h])); FR_HIP(hipFree(B.pcnt[h])); }
-        FR_HIP(hipFree(B.state)); FR_HIP(hipFree(B.teeth)); FR_HIP(hipFree(B.dots)); FR_HIP(hipFree(B.fix_list));
-        FR_HIP(hipFree(B.seq.tiles)); FR_HIP(hipFree(B.seq.subs)); FR_HIP(hipFree(B.seq.total)); FR_HIP(hipFree(B.gnorm));
+        m.release(B.keep); m.release(B.del); m.release(B.S);
+        for (int h = 0; h < 2; h++) { m.release(B.psum[h]); m.release(B.pcnt[h]); }
+        m.release(B.state); m.release(B.teeth); m.release(B.dots); m.release(B.fix_list);
+        m.release(B.seq.tiles); m.release(B.seq.subs); m.release(B.seq.total); m.release(B.seq.tsum); m.release(B.gnorm);
     }
-    F.vals = fr_alloc<double>(cap); F.parent = fr_alloc<uint32_t>(cap);
-    if (!F.st) { F.st = fr_alloc<VecState>(1); F.total = fr_alloc<uint32_t>(2); }
+    F.vals = m.alloc<double>(cap); F.parent = m.alloc<uint32_t>(cap);
+    if (!F.st) { F.st = m.alloc<VecState>(1); F.total = m.alloc<uint32_t>(2); }
     std::swap(c->vc, F.vc);
     c->vc = VcompBuf{};
-    fr_vcomp_alloc(c, cap);
+    fr_vcomp_alloc(c, m, cap);
     std::swap(c->vc, F.vc);
     F.cap = cap;
-}
-void fr_piv_flat_free(FriesCtx *c) {
-    FlatPiv &F = c->flat;
-    if (!F.cap) return;
-    hipFree(F.vals); hipFree(F.parent); hipFree(F.st); hipFree(F.total);
-    VcompBuf &B = F.vc;
-    hipFree(B.keep); hipFree(B.del); hipFree(B.S);
-    for (int h = 0; h < 2; h++) { hipFree(B.psum[h]); hipFree(B.pcnt[h]); }
-    hipFree(B.state); hipFree(B.teeth); hipFree(B.dots); hipFree(B.fix_list);
-    hipFree(B.seq.tiles); hipFree(B.seq.subs); hipFree(B.seq.total); hipFree(B.gnorm);
-    PivBuf &P = F.piv;
-    if (P.start) { hipFree(P.start); hipFree(P.carry); hipFree(P.U); hipFree(P.unit); hipFree(P.scal); }
-    if (P.tile_dd) hipFree(P.tile_dd);
-    F = FlatPiv{};
 }
 void fr_piv_comp_flat(FriesCtx *c, uint32_t n, uint32_t compress_size) {
     FlatPiv &F = c->flat;
@@ -668,7 +654,7 @@ void fr_test_piv_adjust(FriesCtx *c, uint32_t *n_loc_io, double exp_loc, uint32_
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     const uint32_t bound = c->h_vst.curr_size ? c->h_vst.curr_size : 1;
     PivBuf &P = c->piv;
-    piv_alloc(c, P, c->vec.cap);
+    piv_alloc(c->mem, P, c->vec.cap);
     FR_HIP(hipMemsetAsync(P.scal, 0, sizeof(PivScal), st));
     const double top = ceill(exp_loc);
     const double unit_t = tot_norm / n_tot;

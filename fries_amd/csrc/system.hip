@@ -53,8 +53,8 @@ void fr_system_upload(FriesCtx *c, uint32_t n_orb, uint32_t n_elec, const uint8_
     if (n_elec % 2 || n_elec < 2 || n_elec / 2 >= n_orb) throw FriesError("n_elec must be even and leave at least one virtual orbital per spin");
     c->n_orb = n_orb; c->n_elec = n_elec;
     size_t np = (size_t)n_orb * (n_orb + 1) / 2, ne = np * (np + 1) / 2;
-    c->d_h = fr_alloc<double>((size_t)n_orb * n_orb);
-    c->d_eris = fr_alloc<double>(ne);
+    c->d_h = c->mem.alloc<double>((size_t)n_orb * n_orb);
+    c->d_eris = c->mem.alloc<double>(ne);
     FR_HIP(hipMemcpyAsync(c->d_h, h_core, 8 * (size_t)n_orb * n_orb, hipMemcpyHostToDevice, c->stream));
     FR_HIP(hipMemcpyAsync(c->d_eris, eris, 8 * ne, hipMemcpyHostToDevice, c->stream));
     HbTables &H = c->h_hb;
@@ -69,7 +69,7 @@ void fr_system_upload(FriesCtx *c, uint32_t n_orb, uint32_t n_elec, const uint8_
     }
     H.max_n_symm = 0;
     for (unsigned s = 0; s < 8; s++) if (H.lookup[s][0] > H.max_n_symm) H.max_n_symm = H.lookup[s][0];
-    c->d_hb = fr_alloc<HbTables>(1);
+    c->d_hb = c->mem.alloc<HbTables>(1);
     FR_HIP(hipMemcpyAsync(c->d_hb, &H, sizeof(H), hipMemcpyHostToDevice, c->stream));
     FR_LAUNCH(c, "k_hb_pairs", k_hb_pairs, dim3(fr_blocks(n_orb * n_orb, 64)), dim3(64), c->d_hb, c->d_eris, n_orb);
     FR_LAUNCH(c, "k_hb_rows", k_hb_rows, dim3(1), dim3(64), c->d_hb, n_orb);
@@ -77,12 +77,12 @@ void fr_system_upload(FriesCtx *c, uint32_t n_orb, uint32_t n_elec, const uint8_
     // Hartree-Fock determinant and its diagonal element (frisys_mol.cpp:90-101)
     det_t half = (1ull << (n_elec / 2)) - 1ull;
     c->hf_det = half | (half << n_orb);
-    det_t *dd = fr_alloc<det_t>(1); double *de = fr_alloc<double>(1);
+    DevMem tmp;
+    det_t *dd = tmp.alloc<det_t>(1); double *de = tmp.alloc<double>(1);
     FR_HIP(hipMemcpyAsync(dd, &c->hf_det, 8, hipMemcpyHostToDevice, c->stream));
     FR_LAUNCH(c, "k_diag_list", k_diag_list, dim3(1), dim3(64), dd, 1u, c->d_h, c->d_eris, n_orb, 0.0, de);
     FR_HIP(hipMemcpyAsync(&c->hf_en, de, 8, hipMemcpyDeviceToHost, c->stream));
     FR_HIP(hipStreamSynchronize(c->stream));
-    FR_HIP(hipFree(dd)); FR_HIP(hipFree(de));
 }
 
 // ------------------------------------------------------------------ full excitation enumeration
@@ -182,16 +182,17 @@ __global__ void __launch_bounds__(FR_BLOCK) k_enum(const det_t *src, const doubl
 // symmetry-allowed singles and then its doubles as (from position, to determinant, <to|H|from> * parity * -eps).  Excitations whose
 // element is zero are counted (they are part of tot_dense_h, which the matrix sample budget is reduced by, :421) but not stored:
 // the reference's add() drops a zero value.
-void fr_dense_h_setup(FriesCtx *c) {
+void fr_dense_h_setup(FriesCtx *c, DevMem &m) {
     hipStream_t st = c->stream;
     const uint32_t ns = c->vec.n_dense;
     c->n_dense_h = c->n_dense_h_nz = 0;
-    if (!c->d_dense_norm) c->d_dense_norm = fr_alloc<double>(1);
+    if (!c->d_dense_norm) c->d_dense_norm = m.alloc<double>(1);
     if (!ns) return;
     SysDev S; S.n_orb = c->n_orb; S.n_elec = c->n_elec; S.h_core = c->d_h; S.eris = c->d_eris; S.hb = c->d_hb; S.hf_en = c->hf_en; S.spin_parity = c->spin_parity;
     std::vector<double> ones(ns, 1.0);
-    double *d_val = fr_alloc<double>(ns);
-    uint32_t *d_cnt = fr_alloc<uint32_t>(2 * ns), *d_nz = fr_alloc<uint32_t>(2 * ns), *d_off = fr_alloc<uint32_t>(2 * ns);
+    DevMem tmp;
+    double *d_val = tmp.alloc<double>(ns);
+    uint32_t *d_cnt = tmp.alloc<uint32_t>(2 * ns), *d_nz = tmp.alloc<uint32_t>(2 * ns), *d_off = tmp.alloc<uint32_t>(2 * ns);
     FR_HIP(hipMemcpyAsync(d_val, ones.data(), 8 * (size_t)ns, hipMemcpyHostToDevice, st));
     EnumOut eo{nullptr, nullptr, nullptr};
     for (int mode = 0; mode < 2; mode++)
@@ -206,7 +207,7 @@ void fr_dense_h_setup(FriesCtx *c) {
         for (int mode = 0; mode < 2; mode++) { tot += cnt[2 * d + mode]; off[2 * d + mode] = o; o += nz[2 * d + mode]; from.insert(from.end(), nz[2 * d + mode], d); }
     if (tot > 0xffffffffull) throw FriesError("dense block of H too large");
     c->n_dense_h = (uint32_t)tot; c->n_dense_h_nz = o;
-    c->d_dh_from = fr_alloc<uint32_t>(o ? o : 1); c->d_dh_to = fr_alloc<det_t>(o ? o : 1); c->d_dh_el = fr_alloc<double>(o ? o : 1);
+    c->d_dh_from = m.alloc<uint32_t>(o); c->d_dh_to = m.alloc<det_t>(o); c->d_dh_el = m.alloc<double>(o);
     if (o) {
         FR_HIP(hipMemcpyAsync(d_off, off.data(), 8 * (size_t)ns, hipMemcpyHostToDevice, st));
         FR_HIP(hipMemcpyAsync(c->d_dh_from, from.data(), 4 * (size_t)o, hipMemcpyHostToDevice, st));
@@ -215,7 +216,6 @@ void fr_dense_h_setup(FriesCtx *c) {
             FR_LAUNCH(c, "k_enum", k_enum, dim3(ns), dim3(FR_BLOCK), c->vec.dets, d_val, ns, S, mode, 1, d_cnt, d_nz, d_off, wo, -c->eps);
     }
     FR_HIP(hipStreamSynchronize(st));
-    FR_HIP(hipFree(d_val)); FR_HIP(hipFree(d_cnt)); FR_HIP(hipFree(d_nz)); FR_HIP(hipFree(d_off));
 }
 
 // H * trial with trial = the list (src, src_val): returns on the host the merged (det, value)
@@ -226,8 +226,9 @@ void fr_h_apply_list(FriesCtx *c, const std::vector<det_t> &src, const std::vect
     hipStream_t st = c->stream;
     uint32_t ns = (uint32_t)src.size();
     SysDev S; S.n_orb = c->n_orb; S.n_elec = c->n_elec; S.h_core = c->d_h; S.eris = c->d_eris; S.hb = c->d_hb; S.hf_en = c->hf_en; S.spin_parity = c->spin_parity;
-    det_t *d_src = fr_alloc<det_t>(ns); double *d_val = fr_alloc<double>(ns);
-    uint32_t *d_cnt = fr_alloc<uint32_t>(2 * ns), *d_nz = fr_alloc<uint32_t>(2 * ns), *d_off = fr_alloc<uint32_t>(2 * ns);
+    DevMem tmp;      // everything below is this call's own, the temporary vector and spawn buffers included
+    det_t *d_src = tmp.alloc<det_t>(ns); double *d_val = tmp.alloc<double>(ns);
+    uint32_t *d_cnt = tmp.alloc<uint32_t>(2 * ns), *d_nz = tmp.alloc<uint32_t>(2 * ns), *d_off = tmp.alloc<uint32_t>(2 * ns);
     FR_HIP(hipMemcpyAsync(d_src, src.data(), 8 * (size_t)ns, hipMemcpyHostToDevice, st));
     FR_HIP(hipMemcpyAsync(d_val, val.data(), 8 * (size_t)ns, hipMemcpyHostToDevice, st));
     EnumOut eo{nullptr, nullptr, nullptr};
@@ -247,12 +248,11 @@ void fr_h_apply_list(FriesCtx *c, const std::vector<det_t> &src, const std::vect
     FR_HIP(hipMemcpyAsync(d_off, off.data(), 8 * (size_t)ns, hipMemcpyHostToDevice, st));
     // temporary vector with the merge machinery's own spawn buffers
     VecDev hv{};
-    fr_vec_alloc(c, &hv, total + 16);
-    SpawnBuf saved = c->sp;
-    SpawnBuf tmp{};
-    c->sp = tmp;
-    fr_spawn_alloc(c, total + 16);
-    uint32_t *d_orbs = fr_alloc<uint32_t>(total + 16);
+    fr_vec_alloc(c, tmp, &hv, total + 16);
+    struct PutBack { SpawnBuf &sp; SpawnBuf saved; ~PutBack() { sp = saved; } } put_back{c->sp, c->sp};     // the context's spawn buffers come back whatever happens
+    c->sp = SpawnBuf{};
+    fr_spawn_alloc(c, tmp, total + 16);
+    uint32_t *d_orbs = tmp.alloc<uint32_t>(total + 16);
     eo.det = c->sp.det; eo.val = c->sp.val; eo.orbs = d_orbs;
     FR_HIP(hipMemcpyAsync(c->sp.det, src.data(), 8 * (size_t)ns, hipMemcpyHostToDevice, st));
     FR_HIP(hipMemsetAsync(c->sp.val, 0, 8 * (size_t)ns, st));      // the sources enter with value 0 in column 1 ...
@@ -269,7 +269,7 @@ void fr_h_apply_list(FriesCtx *c, const std::vector<det_t> &src, const std::vect
     uint32_t nout = hs.curr_size;
     FR_HIP(hipMemcpy(hd.data(), hv.dets, 8 * (size_t)nout, hipMemcpyDeviceToHost));
     FR_HIP(hipMemcpy(v1.data(), hv.v1, 8 * (size_t)nout, hipMemcpyDeviceToHost));
-    double *d_diag = fr_alloc<double>(ns);
+    double *d_diag = tmp.alloc<double>(ns);
     FR_LAUNCH(c, "k_diag_list", k_diag_list, dim3(fr_blocks(ns, 64)), dim3(64), d_src, ns, c->d_h, c->d_eris, c->n_orb, c->hf_en, d_diag);
     std::vector<double> dg(ns);
     FR_HIP(hipMemcpyAsync(dg.data(), d_diag, 8 * (size_t)ns, hipMemcpyDeviceToHost, st));
@@ -282,14 +282,6 @@ void fr_h_apply_list(FriesCtx *c, const std::vector<det_t> &src, const std::vect
         if (with_diag && i < ns && val[i] != 0) c0 = val[i] * (0 + 1 * dg[i]);
         out_val[i] = c0 + v1[i] * 1.0;
     }
-    // release temporaries
-    SpawnBuf used = c->sp;
-    c->sp = saved;
-    hipFree(used.det); hipFree(used.val); hipFree(used.ini); hipFree(used.slot); hipFree(used.flag);
-    for (int h2 = 0; h2 < 2; h2++) { hipFree(used.key[h2]); hipFree(used.pay[h2]); }
-    hipFree(used.hist); hipFree(used.pcnt); hipFree(used.n_spawn);
-    hipFree(hv.dets); hipFree(hv.v0); hipFree(hv.v1); hipFree(hv.diag); hipFree(hv.active); hipFree(hv.free_stack); hipFree(hv.hs); hipFree(hv.stat_part); hipFree(hv.st);
-    hipFree(d_src); hipFree(d_val); hipFree(d_cnt); hipFree(d_nz); hipFree(d_off); hipFree(d_orbs); hipFree(d_diag);
 }
 
 void fr_h_trial_setup(FriesCtx *c) {
@@ -330,8 +322,8 @@ void fr_h_trial_setup(FriesCtx *c) {
         }
     }
     c->n_trial = (uint32_t)src.size(); c->n_htrial = (uint32_t)od.size();
-    c->tr_det = fr_alloc<det_t>(src.size()); c->tr_val = fr_alloc<double>(src.size());
-    c->htr_det = fr_alloc<det_t>(od.size()); c->htr_val = fr_alloc<double>(od.size());
+    c->tr_det = c->mem.alloc<det_t>(src.size()); c->tr_val = c->mem.alloc<double>(src.size());
+    c->htr_det = c->mem.alloc<det_t>(od.size()); c->htr_val = c->mem.alloc<double>(od.size());
     FR_HIP(hipMemcpy(c->tr_det, src.data(), 8 * src.size(), hipMemcpyHostToDevice));
     FR_HIP(hipMemcpy(c->tr_val, val.data(), 8 * val.size(), hipMemcpyHostToDevice));
     FR_HIP(hipMemcpy(c->htr_det, od.data(), 8 * od.size(), hipMemcpyHostToDevice));
@@ -385,6 +377,15 @@ __global__ void __launch_bounds__(FR_BLOCK) k_src_write(VecDev V, const uint32_t
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_out = off + tot;
 }
 
+// the per-determinant counts / offsets and the source list, sized for the whole vector
+static void full_reserve(FriesCtx *c) {
+    DevMem &m = c->mem;
+    m.release(c->full_cnt); m.release(c->full_nz); m.release(c->full_off); m.release(c->full_list);
+    c->full_cap = c->vec.cap;
+    c->full_cnt = m.alloc<uint32_t>(2 * (size_t)c->full_cap); c->full_nz = m.alloc<uint32_t>(2 * (size_t)c->full_cap); c->full_off = m.alloc<uint32_t>(2 * (size_t)c->full_cap);
+    c->full_list = m.alloc<uint32_t>(c->full_cap);
+}
+
 // h_op_offdiag (molecule.cpp:448-665, spin_parity 0) from column 0 into column 1: every symmetry-allowed single excitation of
 // every stored determinant in storage order, then every double, each worth value * h_fac * <j|H|i>; the annihilating
 // merge takes them in that order.  The spawn buffer holds sp.cap entries, so the list is produced and merged in chunks of
@@ -397,12 +398,7 @@ static uint64_t fr_h_offdiag_vec_ranks(FriesCtx *c, double h_fac) {
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     const uint32_t ns = c->h_vst.curr_size;
     SysDev S; S.n_orb = c->n_orb; S.n_elec = c->n_elec; S.h_core = c->d_h; S.eris = c->d_eris; S.hb = c->d_hb; S.hf_en = c->hf_en; S.spin_parity = c->spin_parity;
-    if (c->full_cap < ns || !c->full_cnt) {
-        if (c->full_cnt) { FR_HIP(hipFree(c->full_cnt)); FR_HIP(hipFree(c->full_nz)); FR_HIP(hipFree(c->full_off)); FR_HIP(hipFree(c->full_list)); }
-        c->full_cap = c->vec.cap;
-        c->full_cnt = fr_alloc<uint32_t>(2 * (size_t)c->full_cap); c->full_nz = fr_alloc<uint32_t>(2 * (size_t)c->full_cap); c->full_off = fr_alloc<uint32_t>(2 * (size_t)c->full_cap);
-        c->full_list = fr_alloc<uint32_t>(c->full_cap);
-    }
+    if (c->full_cap < ns || !c->full_cnt) full_reserve(c);
     uint32_t nl = 0;
     if (ns) {
         const unsigned gt = fr_blocks(ns, FR_TILE);
@@ -452,12 +448,7 @@ uint64_t fr_h_offdiag_vec(FriesCtx *c, double h_fac) {
     const uint32_t ns = c->h_vst.curr_size;
     if (ns == 0) return 0;
     SysDev S; S.n_orb = c->n_orb; S.n_elec = c->n_elec; S.h_core = c->d_h; S.eris = c->d_eris; S.hb = c->d_hb; S.hf_en = c->hf_en; S.spin_parity = c->spin_parity;
-    if (c->full_cap < ns) {
-        if (c->full_cnt) { FR_HIP(hipFree(c->full_cnt)); FR_HIP(hipFree(c->full_nz)); FR_HIP(hipFree(c->full_off)); FR_HIP(hipFree(c->full_list)); }
-        c->full_cap = c->vec.cap;
-        c->full_cnt = fr_alloc<uint32_t>(2 * (size_t)c->full_cap); c->full_nz = fr_alloc<uint32_t>(2 * (size_t)c->full_cap); c->full_off = fr_alloc<uint32_t>(2 * (size_t)c->full_cap);
-        c->full_list = fr_alloc<uint32_t>(c->full_cap);
-    }
+    if (c->full_cap < ns) full_reserve(c);
     // the determinants with a non-zero value, in storage order
     const unsigned gt = fr_blocks(ns, FR_TILE);
     FR_LAUNCH(c, "k_src_count", k_src_count, dim3(gt), dim3(FR_BLOCK), c->vec, c->sp.pcnt);

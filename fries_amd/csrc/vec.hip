@@ -23,19 +23,19 @@ static void fr_hash_clear(FriesCtx *c, VecDev *v, uint32_t n_slots) {
     unsigned g = fr_blocks(n_slots, FR_BLOCK);
     FR_LAUNCH(c, "k_hash_clear", k_hash_clear, dim3(g > 2048 ? 2048 : g), dim3(FR_BLOCK), v->hs, n_slots);
 }
-void fr_vec_alloc(FriesCtx *c, VecDev *v, uint32_t cap) {
+void fr_vec_alloc(FriesCtx *c, DevMem &m, VecDev *v, uint32_t cap) {
     v->cap = cap; v->n_dense = 0;
     uint32_t h = 1024;
     while (h < 2u * cap + 1024u) h <<= 1;
     v->hcap_max = h;
     v->hcap = h < (1u << 14) ? h : (1u << 14);
     v->used_ub = 0;
-    v->dets = fr_alloc<det_t>(cap); v->v0 = fr_alloc<double>(cap); v->v1 = fr_alloc<double>(cap);
-    v->diag = fr_alloc<double>(cap); v->active = fr_alloc<uint8_t>(cap); v->free_stack = fr_alloc<uint32_t>(cap);
-    v->hs = fr_alloc<HSlot>(h);
-    v->stat_part = fr_alloc<unsigned long long>((size_t)FR_STAT_STRIPES * FR_STAT_STRIDE);
+    v->dets = m.alloc<det_t>(cap); v->v0 = m.alloc<double>(cap); v->v1 = m.alloc<double>(cap);
+    v->diag = m.alloc<double>(cap); v->active = m.alloc<uint8_t>(cap); v->free_stack = m.alloc<uint32_t>(cap);
+    v->hs = m.alloc<HSlot>(h);
+    v->stat_part = m.alloc<unsigned long long>((size_t)FR_STAT_STRIPES * FR_STAT_STRIDE);
     FR_HIP(hipMemsetAsync(v->stat_part, 0, 8 * (size_t)FR_STAT_STRIPES * FR_STAT_STRIDE, c->stream));
-    v->st = fr_alloc<VecState>(1);
+    v->st = m.alloc<VecState>(1);
     FR_HIP(hipMemsetAsync(v->dets, 0, sizeof(det_t) * cap, c->stream));
     FR_HIP(hipMemsetAsync(v->v0, 0, 8 * (size_t)cap, c->stream));
     FR_HIP(hipMemsetAsync(v->v1, 0, 8 * (size_t)cap, c->stream));
@@ -50,11 +50,10 @@ static __global__ void __launch_bounds__(64) k_readback(const uint32_t *src, uin
     for (unsigned i = threadIdx.x; i < n_words; i += 64) dst[i] = src[i];
     if (word && threadIdx.x == 0) __hip_atomic_store(word, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);      // one wave: the release waits for every lane's stores
 }
-void fr_rb_init(FriesCtx *c) {
+void fr_rb_init(FriesCtx *c, DevMem &m) {
     if (c->h_rb) return;
-    void *hp = nullptr, *dp = nullptr;
     const size_t tot = FriesCtx::RB_BYTES + FriesCtx::RB_HELD_BYTES + FriesCtx::MISC_BYTES;
-    FR_HIP(hipHostMalloc(&hp, tot, hipHostMallocMapped | hipHostMallocCoherent));
+    void *hp = m.alloc_pinned<uint8_t>(tot, true), *dp = nullptr;
     FR_HIP(hipHostGetDevicePointer(&dp, hp, 0));
     memset(hp, 0, tot);
     c->h_rb = (uint8_t *)hp; c->d_rb = (uint8_t *)dp; c->rb_used = 0;
@@ -64,7 +63,7 @@ static __global__ void k_ticket(uint32_t *word, uint32_t ticket) { __hip_atomic_
 // The wait in two halves: the ticket is enqueued where the host needs the stream's results, kernels enqueued after it run while the host
 // waits for it (run_stage: the kernels that follow a stage's closing pass, which leave at once if the pass did not settle the stage).
 uint32_t fr_stream_ticket(FriesCtx *c) {
-    fr_rb_init(c);
+    fr_rb_init(c, c->mem);
     if (c->wait_by_sync) return 0u;
     const uint32_t t = ++c->ticket;
     FR_LAUNCH(c, "k_ticket", k_ticket, dim3(1), dim3(1), c->d_misc(), t);
@@ -73,7 +72,7 @@ uint32_t fr_stream_ticket(FriesCtx *c) {
 // A ticket that a kernel of the caller's raises itself (k_readback at its end; k_seq_sums when it STARTS: everything enqueued before it has finished
 // then, which is all a ticket says) -- no launch of its own.  0: the host waits by hipStreamSynchronize, nobody raises anything.
 uint32_t fr_ticket_reserve(FriesCtx *c) {
-    fr_rb_init(c);
+    fr_rb_init(c, c->mem);
     if (c->wait_by_sync) return 0u;
     return ++c->ticket;
 }
@@ -93,7 +92,7 @@ void fr_stream_wait_ticket(FriesCtx *c, uint32_t t) {
 }
 void fr_stream_wait(FriesCtx *c) { fr_stream_wait_ticket(c, fr_stream_ticket(c)); }
 static size_t fr_rb_take(FriesCtx *c, size_t bytes, bool held) {
-    fr_rb_init(c);
+    fr_rb_init(c, c->mem);
     const size_t need = (bytes + 63) & ~(size_t)63;
     if (bytes == 0 || (bytes & 3) || need > 2048) throw FriesError("fr_readback: bad size");
     if (held) return FriesCtx::RB_BYTES;        // a slot of its own behind the ring: the ring may wrap any number of times before the caller reads it
@@ -137,15 +136,15 @@ void fr_vec_sync_state(FriesCtx *c, VecDev *v, VecState *out) {
     v->used_ub = out->n_used;
 }
 
-void fr_spawn_alloc(FriesCtx *c, uint32_t cap) {
+void fr_spawn_alloc(FriesCtx *c, DevMem &m, uint32_t cap) {
     SpawnBuf &s = c->sp;
     s.cap = cap;
-    s.det = fr_alloc<det_t>(cap); s.val = fr_alloc<double>(cap); s.ini = fr_alloc<uint8_t>(cap);
-    s.slot = fr_alloc<uint32_t>(cap); s.flag = fr_alloc<uint32_t>(cap);
-    for (int h = 0; h < 2; h++) { s.key[h] = fr_alloc<uint32_t>(cap); s.pay[h] = fr_alloc<uint32_t>(cap); }
-    s.hist = fr_alloc<uint32_t>((size_t)256 * FR_MAX_PART + 256);
-    s.pcnt = fr_alloc<uint32_t>(FR_MAX_PART);
-    s.n_spawn = fr_alloc<uint32_t>(1);
+    s.det = m.alloc<det_t>(cap); s.val = m.alloc<double>(cap); s.ini = m.alloc<uint8_t>(cap);
+    s.slot = m.alloc<uint32_t>(cap); s.flag = m.alloc<uint32_t>(cap);
+    for (int h = 0; h < 2; h++) { s.key[h] = m.alloc<uint32_t>(cap); s.pay[h] = m.alloc<uint32_t>(cap); }
+    s.hist = m.alloc<uint32_t>((size_t)256 * FR_MAX_PART + 256);
+    s.pcnt = m.alloc<uint32_t>(FR_MAX_PART);
+    s.n_spawn = m.alloc<uint32_t>(1);
     FR_HIP(hipMemsetAsync(s.n_spawn, 0, 4, c->stream));
 }
 
@@ -805,14 +804,14 @@ __global__ void __launch_bounds__(FR_BLOCK) k_xch_rounds(const uint8_t *key, con
     }
 }
 
-void fr_xch_alloc(FriesCtx *c, uint32_t cap) {
+void fr_xch_alloc(FriesCtx *c, DevMem &m, uint32_t cap) {
     SpawnBuf &S = c->sp;
     if (!c->use_comm) return;
     uint32_t ntile = fr_blocks(cap, FR_BLOCK) + 1;
-    S.xkey = fr_alloc<uint8_t>(cap);
-    S.xcnt = fr_alloc<uint32_t>((size_t)ntile * 2 * c->n_ranks);
-    S.xoff = fr_alloc<uint32_t>((size_t)ntile * 2 * c->n_ranks);
-    S.xbucket = fr_alloc<uint32_t>(4 * (size_t)c->n_ranks);
+    S.xkey = m.alloc<uint8_t>(cap);
+    S.xcnt = m.alloc<uint32_t>((size_t)ntile * 2 * c->n_ranks);
+    S.xoff = m.alloc<uint32_t>((size_t)ntile * 2 * c->n_ranks);
+    S.xbucket = m.alloc<uint32_t>(4 * (size_t)c->n_ranks);
     if ((uint64_t)cap * sizeof(XchRec) > c->comm.big_bytes) throw FriesError("fries_comm.big_bytes is smaller than 16 bytes x (mat_nonz + 4096)");
     if ((size_t)2 * c->n_ranks * 4 > 2048) throw FriesError("too many ranks");
 }
@@ -880,8 +879,9 @@ static uint32_t fr_xch_rounds(FriesCtx *c, uint32_t n_local) {
     hipStream_t st = c->stream;
     const int P = c->n_ranks;
     if (!S.bdet) {
-        S.bdet = fr_alloc<det_t>(S.cap); S.bval = fr_alloc<double>(S.cap); S.bini = fr_alloc<uint8_t>(S.cap); S.bn = fr_alloc<uint32_t>(1);
-        S.xbounds = fr_alloc<uint32_t>(2 * (FR_XCH_MAXR + 2));
+        DevMem &m = c->mem;
+        S.bdet = m.alloc<det_t>(S.cap); S.bval = m.alloc<double>(S.cap); S.bini = m.alloc<uint8_t>(S.cap); S.bn = m.alloc<uint32_t>(1);
+        S.xbounds = m.alloc<uint32_t>(2 * (FR_XCH_MAXR + 2));
     }
     FR_HIP(hipMemcpyAsync(S.bdet, S.det, sizeof(det_t) * (size_t)n_local, hipMemcpyDeviceToDevice, st));
     FR_HIP(hipMemcpyAsync(S.bval, S.val, 8 * (size_t)n_local, hipMemcpyDeviceToDevice, st));

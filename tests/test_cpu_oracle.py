@@ -537,6 +537,19 @@ def test_product_never_imports_oracle():
                 assert "oracle" not in txt.lower() or fn == "engine.py" and False, os.path.join(dirpath, fn)
 
 
+def test_device_memory_has_one_owner():
+    """device and pinned memory is allocated and freed in csrc/devmem.hpp only: every array belongs to a DevMem, which frees it"""
+    import re
+    csrc = os.path.join(ROOT, "fries_amd", "csrc")
+    sources = [fn for fn in sorted(os.listdir(csrc)) if fn.endswith((".hip", ".hpp"))]
+    assert "devmem.hpp" in sources and len(sources) > 10
+    for fn in sources:
+        if fn == "devmem.hpp":
+            continue
+        for no, line in enumerate(open(os.path.join(csrc, fn), errors="ignore"), 1):
+            assert not re.search("hipMalloc|hipHostMalloc|hipFree|hipHostFree", line), (fn, no, line.strip()[:120])
+
+
 def _check_checkpoint_shards(d):
     """-> number of stored determinants of the checkpoint directory d that were checked (see the test below)."""
     import oracle_lib
