@@ -325,3 +325,5 @@ void fr_system_upload(FriesCtx *c, uint32_t n_orb, uint32_t n_elec, const uint8_
 void fr_h_trial_setup(FriesCtx *c);
 void fr_h_diag_vec(FriesCtx *c, double id_fac, double h_fac);
 uint64_t fr_h_offdiag_vec(FriesCtx *c, double h_fac);
+// hdot.hip
+void fr_h_dot(FriesCtx *a, FriesCtx *b, fries_hdot_result *out);

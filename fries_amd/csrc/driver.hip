@@ -1007,6 +1007,14 @@ extern "C" int fries_h_offdiag_list(fries_ctx *h, const uint64_t *dets, const do
     FR_API_END
 }
 
+// calc_h_dot (molecule.cpp:667-885) between two contexts' vectors: hdot.hip
+extern "C" int fries_h_dot(fries_ctx *a, fries_ctx *b, fries_hdot_result *out) {
+    FR_API_BEGIN
+    if (!a || !b || !out) throw FriesError("fries_h_dot: null argument");
+    fr_h_dot(&a->c, &b->c, out);
+    FR_API_END
+}
+
 extern "C" int fries_set_vec_scrambler(fries_ctx *h, const uint32_t *vec_scr, size_t n) {
     FR_API_BEGIN
     FriesCtx *c = &h->c;

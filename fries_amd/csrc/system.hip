@@ -5,6 +5,7 @@
 // tables are bit-identical to the CPU ones.
 #include "ctx.hpp"
 #include "hbpp_rows.hpp"
+#include "enum_rows.hpp"
 #include <cstring>
 
 __global__ void k_hb_pairs(HbTables *T, const double *eris, unsigned n) {
@@ -91,80 +92,28 @@ void fr_system_upload(FriesCtx *c, uint32_t n_orb, uint32_t n_elec, const uint8_
 // mode 0: singles (sing_ex_symm), 1: doubles (doub_ex_symm).  pass 0 counts, pass 1 writes.
 struct EnumOut { det_t *det; double *val; uint32_t *orbs; };
 
-__device__ __forceinline__ bool fr_enum_candidate(const HbTables &T, det_t det, int mode, uint32_t idx, unsigned *o1, unsigned *o2, unsigned *u1, unsigned *u2) {
-    const unsigned n = T.n_orb, ne = T.n_elec, h = ne / 2;
-    if (mode == 0) {
-        // (electron i, orbital a of the same spin)
-        unsigned i = idx / n, a = idx % n;
-        if (i >= ne) return false;
-        unsigned sp = i / h, io = fr_nth_bit(det, i), ao = a + sp * n;
-        if (fr_bit(det, ao) || T.irrep[io % n] != T.irrep[a]) return false;
-        *o1 = io; *u1 = ao; *o2 = 0; *u2 = 0;
-        return true;
-    }
-    const uint32_t n_os = h * h * n * n, npair = h * (h - 1) / 2, n_ss = npair * n * n;
-    if (idx < n_os) {
-        unsigned l = idx % n, k = (idx / n) % n, j = (idx / (n * n)) % h, i = idx / (n * n * h);
-        unsigned io = fr_nth_bit(det, i), jo = fr_nth_bit(det, h + j), ko = k, lo = l + n;
-        if (fr_bit(det, ko) || fr_bit(det, lo)) return false;
-        if ((T.irrep[io] ^ T.irrep[jo - n] ^ T.irrep[k] ^ T.irrep[l]) != 0) return false;
-        *o1 = io; *o2 = jo; *u1 = ko; *u2 = lo;
-        return true;
-    }
-    idx -= n_os;
-    unsigned sp = 0;
-    if (idx >= n_ss) { idx -= n_ss; sp = 1; if (idx >= n_ss) return false; }
-    unsigned l = idx % n, k = (idx / n) % n, pr = idx / (n * n);
-    if (l <= k) return false;
-    // pair index -> (i < j) in the order i outer, j inner
-    unsigned i = 0, rem = pr;
-    while (rem >= h - 1 - i) { rem -= h - 1 - i; i++; }
-    unsigned j = i + 1 + rem;
-    unsigned io = fr_nth_bit(det, sp * h + i), jo = fr_nth_bit(det, sp * h + j), ko = k + sp * n, lo = l + sp * n;
-    if (fr_bit(det, ko) || fr_bit(det, lo)) return false;
-    if ((T.irrep[io % n] ^ T.irrep[jo % n] ^ T.irrep[k] ^ T.irrep[l]) != 0) return false;
-    *o1 = io; *o2 = jo; *u1 = ko; *u2 = lo;
-    return true;
-}
-
 // counts[2*d + mode] = symmetry-allowed excitations; nz[2*d+mode] = those with a non-zero element
 __global__ void __launch_bounds__(FR_BLOCK) k_enum(const det_t *src, const double *src_val, uint32_t n_src, SysDev S, int mode, int pass,
                                                    uint32_t *counts, uint32_t *nz, const uint32_t *offsets, EnumOut out, double h_fac, const uint32_t *src_idx = nullptr) {
     __shared__ HbTables T;
     __shared__ uint32_t shu[4];
     fr_stage_tables(&T, S.hb);
-    const unsigned n = T.n_orb, ne = T.n_elec, h = ne / 2;
+    const unsigned n = T.n_orb, ne = T.n_elec;
     const uint32_t d = blockIdx.x;              // counts / nz / offsets are indexed by list entry
     if (d >= n_src) return;
     const uint32_t at = src_idx ? src_idx[d] : d;
     const det_t det = src[at];
     const double cur = src_val[at];
-    uint32_t n_cand = mode == 0 ? ne * n : h * h * n * n + 2 * (h * (h - 1) / 2) * n * n;
+    uint32_t n_cand = fr_enum_n_cand(n, ne, mode);
     uint32_t n_allowed = 0, n_written = 0;
     uint32_t obase = pass ? offsets[2 * d + mode] : 0;
     for (uint32_t c0 = 0; c0 < n_cand; c0 += FR_BLOCK) {
         uint32_t idx = c0 + threadIdx.x;
         unsigned o1, o2, u1, u2;
-        bool ok = idx < n_cand && cur != 0 && fr_enum_candidate(T, det, mode, idx, &o1, &o2, &u1, &u2);
         double m = 0;
         det_t nd = det;
-        if (ok) {
-            if (mode == 0) {
-                m = fr_sing_matrel(det, o1, u1, S.h_core, S.eris, n);
-                nd = det & ~(1ull << o1);
-                int sgn = (fr_bits_between(nd, o1, u1) & 1) ? -1 : 1;       // sing_det_parity, fci_utils.c:46-51
-                nd |= 1ull << u1;
-                m *= sgn;
-            }
-            else {
-                m = fr_doub_matrel(o1, o2, u1, u2, S.eris, n);
-                m *= fr_doub_parity(det, o1, o2, u1, u2);                   // doub_det_parity, fci_utils.c:66-75
-                nd = (det & ~(1ull << o1) & ~(1ull << o2)) | (1ull << u1) | (1ull << u2);
-            }
-            // time-reversal symmetrised vectors: the element between the symmetrised functions, added to the pair's representative
-            if (S.spin_parity) { det_t tgt = nd; if (fr_adjust_tr(T, S, det, nd, &m, S.spin_parity, &tgt, 0, nullptr, 0.0)) nd = tgt; else m = 0; }
-            m *= cur * h_fac;
-        }
+        bool ok = idx < n_cand && cur != 0 && fr_enum_element(T, S, det, mode, idx, &nd, &m, &o1, &o2, &u1, &u2);      // enum_rows.hpp, shared with k_hdot
+        if (ok) m *= cur * h_fac;
         uint32_t f = (ok && m != 0) ? 1u : 0u, tot, tot_ok;
         uint32_t incl_ok = fr_block_scan_u32(ok ? 1u : 0u, shu, &tot_ok);
         (void)incl_ok;

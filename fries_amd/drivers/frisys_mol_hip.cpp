@@ -4,6 +4,7 @@
 //   frisys_mol_hip --fcidump_path F --point_group D2h --distribution HB_unnorm --vec_nonz N --mat_nonz N --max_dets N
 //                  [--target T] [--initiator I] [--epsilon E] [--max_iter K] [--result_dir DIR/] [--load_dir DIR/]
 //                  [--ini_vec PREFIX] [--trial_vec PREFIX] [--det_space FILE] [--ham_shift E] [--seed S] [--device D]
+//                  [--replicas R [--repl_every K]]
 //
 // Host side only: option parsing (argparse there, a loop here), the FCIDUMP reader (parse_fcidump / convert_symm,
 // FRIES/io_utils.cpp:189-318), the text outputs projnum.txt / projden.txt / S.txt / norm.txt / nkept.txt / params.txt
@@ -21,10 +22,23 @@
 //     share a GPU) or on --devices 0,1,...: for machines with fewer GPUs than ranks, and for tests.
 // Every rank writes dets<rank>.dat / vals<rank>.dat; the rank that owns the HF determinant writes the text outputs, rank 0
 // dense.txt and hash.dat (frisys_mol.cpp:288-345, vec_utils.hpp:713-746).  All ranks must be given the same --seed.
+//
+// Replicas (what the reference's obs_repl_mol needs: independent trajectories and the estimator between them):
+//   * --replicas R (1 <= R <= 16; needs --seed; not with --ranks, a launcher's WORLD_SIZE > 1 or --load_dir): R host threads of this
+//     process on --device, each a one-rank run of its own with seed + r that writes <result_dir>replica<r>/ exactly as a plain run with
+//     --seed seed+r --result_dir <result_dir>replica<r>/ would, byte for byte;
+//   * --repl_every K (default 0): after iterations K, 2K, ... and always after the last one the replicas meet, and fries_h_dot is
+//     evaluated for the pairs (0,1), (0,2), ..., (1,2), ... with the shorter vector enumerating (R = 1: the pair (0,0), the vector's
+//     Rayleigh quotient).  One line per evaluation goes to <result_dir>replnum.txt (the h values, comma-separated), replden.txt (the
+//     overlaps) and repliter.txt (the iteration count).  A replica that fails releases the others, and the process returns non-zero.
 #include "driver_common.hpp"
 #include <sstream>
 #include <random>
 #include <thread>
+#include <mutex>
+#include <condition_variable>
+#include <cerrno>
+#include <sys/stat.h>
 #include <unistd.h>
 
 struct Args {
@@ -36,6 +50,7 @@ struct Args {
     bool have_seed = false, have_device = false;
     uint32_t ranks = 0;                 // --ranks: thread ranks inside this process
     std::vector<int> devices;           // --devices: GPU of every thread rank
+    uint32_t replicas = 0, repl_every = 0;      // --replicas / --repl_every: independent runs inside this process and how often they are compared
 };
 
 static Args parse_args(int argc, char **argv) {
@@ -60,6 +75,14 @@ static Args parse_args(int argc, char **argv) {
     if (kv.count("seed")) { r.seed = (uint32_t)std::stoul(kv["seed"]); r.have_seed = true; }
     if (kv.count("device")) { r.device = (uint32_t)std::stoul(kv["device"]); r.have_device = true; }
     if (kv.count("ranks")) r.ranks = (uint32_t)std::stoul(kv["ranks"]);
+    if (kv.count("replicas")) {
+        r.replicas = (uint32_t)std::stoul(kv["replicas"]);
+        if (r.replicas < 1 || r.replicas > 16) throw std::runtime_error("--replicas must be between 1 and 16");
+    }
+    if (kv.count("repl_every")) {
+        if (!r.replicas) throw std::runtime_error("--repl_every needs --replicas");
+        r.repl_every = (uint32_t)std::stoul(kv["repl_every"]);
+    }
     if (kv.count("devices")) { std::stringstream ss(kv["devices"]); std::string t; while (std::getline(ss, t, ',')) r.devices.push_back(std::stoi(t)); }
     return r;
 }
@@ -128,10 +151,63 @@ static bool load_last_line(const std::string &path, double *out) {
     return any;
 }
 
-// one rank of the run (the body of the reference's main after MPI_Init): `tr` == nullptr is the one-rank run
-static void run_rank(const Args &args, const Fcidump &in, uint32_t seed, int rank, int n_ranks, int device, fries_transport *tr) {
+// --replicas: where the replica threads meet.  The last one to arrive evaluates the pairs while the others wait, so no context is
+// inside another call during fries_h_dot; a replica that fails calls abort(), which sends every waiting and every later arrival home
+// with an exception instead of leaving it at a barrier nobody else will reach.
+struct Replicas {
+    const int R, precision;
+    std::vector<fries_ctx *> ctx;
+    std::ofstream num_file, den_file, iter_file;
+    std::mutex mu;
+    std::condition_variable cv;
+    int arrived = 0; uint64_t generation = 0; bool aborted = false;
+    Replicas(int R_, const Args &args) : R(R_), precision(args.precision), ctx((size_t)R_, nullptr) {
+        const std::string &rd = args.result_dir;
+        num_file.open(rd + "replnum.txt", std::ofstream::app); den_file.open(rd + "replden.txt", std::ofstream::app); iter_file.open(rd + "repliter.txt", std::ofstream::app);
+        if (!num_file.is_open() || !den_file.is_open() || !iter_file.is_open()) throw std::runtime_error("Could not open file for writing in directory " + rd);
+        num_file.precision(precision); den_file.precision(precision);
+    }
+    void abort() { std::lock_guard<std::mutex> lk(mu); aborted = true; cv.notify_all(); }
+    // fries_h_dot for every pair, the shorter vector enumerating (the estimate is symmetric up to rounding)
+    void evaluate(uint32_t iters_done) {
+        std::vector<int32_t> nz((size_t)R, 0);
+        for (int r = 0; r < R; r++) { uint32_t n, nf; ck(fries_vec_info(ctx[r], &n, &nz[r], &nf)); }
+        bool first = true;
+        auto one = [&](int r, int s) {
+            const int a = nz[r] <= nz[s] ? r : s, b = a == r ? s : r;
+            fries_hdot_result res;
+            ck(fries_h_dot(ctx[a], ctx[b], &res));
+            if (!first) { num_file << ','; den_file << ','; }
+            first = false;
+            num_file << res.h; den_file << res.ovlp;
+        };
+        if (R == 1) one(0, 0);
+        for (int r = 0; r < R; r++) for (int s = r + 1; s < R; s++) one(r, s);
+        num_file << '\n'; den_file << '\n'; iter_file << iters_done << '\n';
+        num_file.flush(); den_file.flush(); iter_file.flush();
+    }
+    void meet(uint32_t iters_done) {
+        std::unique_lock<std::mutex> lk(mu);
+        if (aborted) throw std::runtime_error("another replica failed");
+        if (++arrived == R) {
+            try { evaluate(iters_done); }
+            catch (...) { aborted = true; cv.notify_all(); throw; }
+            arrived = 0; generation++;
+            cv.notify_all();
+            return;
+        }
+        const uint64_t gen = generation;
+        cv.wait(lk, [&] { return generation != gen || aborted; });
+        if (generation == gen) throw std::runtime_error("another replica failed");
+    }
+};
+
+// one rank of the run (the body of the reference's main after MPI_Init): `tr` == nullptr is the one-rank run; with --replicas, replica
+// `repl_idx` of `repl` (a one-rank run that stops at the meeting points)
+static void run_rank(const Args &args, const Fcidump &in, uint32_t seed, int rank, int n_ranks, int device, fries_transport *tr, Replicas *repl = nullptr, int repl_idx = 0) {
     fries_ctx *ctx = nullptr;
     ck(fries_ctx_create(&ctx, device));
+    if (repl) repl->ctx[(size_t)repl_idx] = ctx;
     ck(fries_set_molecule(ctx, in.n_orb, in.n_elec, in.symm.data(), in.hcore.data(), in.eris.data()));
     if (tr) {
         fries_comm cm;
@@ -215,6 +291,7 @@ static void run_rank(const Args &args, const Fcidump &in, uint32_t seed, int ran
             save_vector(ctx, rd, in.n_orb, rank, n_ranks);
             if (writer) { num_file.flush(); den_file.flush(); shift_file.flush(); nkept_file.flush(); }
         }
+        if (repl && ((args.repl_every && (it + 1) % args.repl_every == 0) || it + 1 == args.max_iter)) repl->meet(it + 1);
     }
     save_vector(ctx, rd, in.n_orb, rank, n_ranks);
     fries_ctx_destroy(ctx);
@@ -228,8 +305,18 @@ static int env_int(const char *a, const char *b, const char *c) {
 
 int main(int argc, char **argv) {
     Args args;
-    try { args = parse_args(argc, argv); if (args.dist != "HB" && args.dist != "HB_unnorm") throw std::runtime_error("\"dist_str\" argument must be either \"HB\" or \"HB_unnorm\""); }
+    try {
+        args = parse_args(argc, argv);
+        if (args.dist != "HB" && args.dist != "HB_unnorm") throw std::runtime_error("\"dist_str\" argument must be either \"HB\" or \"HB_unnorm\"");
+        if (args.replicas) {        // checked here, before any file is read or any device touched
+            if (args.ranks) throw std::runtime_error("--replicas and --ranks exclude each other (each replica is a one-rank run)");
+            if (env_int("WORLD_SIZE", "OMPI_COMM_WORLD_SIZE", "PMI_SIZE") > 1) throw std::runtime_error("--replicas cannot run under a launcher with WORLD_SIZE > 1 (each replica is a one-rank run)");
+            if (!args.load_dir.empty()) throw std::runtime_error("--replicas and --load_dir exclude each other");
+            if (!args.have_seed) throw std::runtime_error("--replicas needs --seed: replica r runs with seed + r");
+        }
+    }
     catch (std::exception &ex) { std::cerr << "\nError parsing command line: " << ex.what() << "\n\n"; return 1; }
+    int rc = 0;
     try {
         Fcidump in = parse_fcidump(args.fcidump_path, args.point_group);
         uint32_t seed = args.seed;
@@ -237,7 +324,26 @@ int main(int argc, char **argv) {
         if ((args.ranks > 1 || env_size > 1) && !args.have_seed) throw std::runtime_error("several ranks need the same --seed on every rank (the reference broadcasts rank 0's draws)");
         if (!args.have_seed) seed = wall_clock_seed();      // frisys_mol.cpp:104-106
         const uint64_t big_bytes = 16ull * ((uint64_t)args.mat_nonz + 4096);
-        if (args.ranks > 1) {
+        if (args.replicas) {
+            // R independent one-rank runs = R threads of this process, started like the --ranks threads below
+            const int R = (int)args.replicas;
+            Replicas repl(R, args);
+            std::vector<std::string> errs((size_t)R);
+            std::vector<std::thread> th;
+            for (int r = 0; r < R; r++)
+                th.emplace_back([&, r] {
+                    try {
+                        Args mine = args;
+                        mine.result_dir = args.result_dir + "replica" + std::to_string(r) + "/";
+                        if (mkdir(mine.result_dir.c_str(), 0777) && errno != EEXIST) throw std::runtime_error("Could not create directory " + mine.result_dir);
+                        run_rank(mine, in, seed + (uint32_t)r, 0, 1, (int)args.device, nullptr, &repl, r);
+                    }
+                    catch (std::exception &ex) { errs[(size_t)r] = ex.what(); repl.abort(); }
+                });
+            for (auto &t : th) t.join();
+            for (int r = 0; r < R; r++) if (!errs[(size_t)r].empty()) { std::cerr << "\nException on replica " << r << " : " << errs[(size_t)r] << "\n"; rc = 2; }
+        }
+        else if (args.ranks > 1) {
             // P ranks = P threads of this process (fries_local_*)
             const int P = (int)args.ranks;
             std::cout << "seed on process 0 is " << seed << std::endl;
@@ -301,6 +407,7 @@ int main(int argc, char **argv) {
         }
     } catch (std::exception &ex) {
         std::cerr << "\nException : " << ex.what() << "\n";       // the reference prints and exits 0 (frisys_mol.cpp:562-566)
+        if (args.replicas) rc = 2;      // (--replicas has no reference behaviour to keep: a failure is a failure code)
     }
-    return 0;
+    return rc;
 }

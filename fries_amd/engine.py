@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -28,6 +29,7 @@ EXPORTS = [
     "fries_set_proc_scrambler", "fries_tie_margins", "fries_measure_copy_bandwidth", "fries_piv_stats", "fries_set_trial_vector", "fries_set_initial_vector", "fries_set_ham_shift", "fries_vec_add_to", "fries_death_clone", "fries_dots", "fries_find_preserve", "fries_sys_comp",
     "fries_vec_column_download", "fries_vec_column_upload", "fries_vec_column_zero", "fries_vec_diag_download", "fries_vec_dot_list", "fries_vec_add_vecs", "fries_set_det_space", "fries_vec_set_dense", "fries_dense_sizes", "fries_hostcomm_create", "fries_set_vec_scrambler", "fries_hh_comp_sub", "fries_hh_ref_ovlp", "fries_set_spin_parity", "fries_h_offdiag_list",
     "fries_spawn_from_comp", "fries_dense_apply", "fries_dense_norm", "fries_dense_h_count", "fries_comp_download",
+    "fries_h_dot",
 ]
 
 
@@ -69,6 +71,26 @@ class IterLog(C.Structure):
     _fields_ = [("numer", C.c_double), ("denom", C.c_double), ("shift", C.c_double), ("norm", C.c_double),
                 ("nkept", C.c_uint32), ("n_nonz", C.c_int32), ("curr_size", C.c_uint32), ("num_success", C.c_uint32),
                 ("comp_len", C.c_uint32 * 5), ("err", C.c_uint32)]
+
+
+class HdotResult(C.Structure):
+    """struct fries_hdot_result"""
+    _fields_ = [("h", C.c_double), ("ovlp", C.c_double), ("abs_sum", C.c_double), ("n_src", C.c_uint64), ("n_terms", C.c_uint64), ("n_hits", C.c_uint64)]
+
+
+class HDot(NamedTuple):
+    """fries_h_dot's result: h = <a|H|b>, ovlp = <a|b>, abs_sum = the sum of the magnitudes of h's terms; the counts of sources,
+    non-zero excitations and excitations found in b."""
+    h: float
+    ovlp: float
+    abs_sum: float
+    n_src: int
+    n_terms: int
+    n_hits: int
+
+    @property
+    def energy(self) -> float:
+        return self.h / self.ovlp
 
 
 ITERLOG_DTYPE = np.dtype([("numer", "f8"), ("denom", "f8"), ("shift", "f8"), ("norm", "f8"), ("nkept", "u4"), ("n_nonz", "i4"),
@@ -170,6 +192,7 @@ def load_library() -> C.CDLL:
     lib.fries_dense_norm.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.fries_dense_h_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     lib.fries_comp_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.fries_h_dot.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(HdotResult)]
     _lib = lib
     return lib
 
@@ -500,6 +523,18 @@ class FriEngine:
         m = C.c_size_t()
         self._ck(self.lib.fries_h_offdiag_list(self.h, _ptr(d), _ptr(v), d.size, _ptr(od), _ptr(ov), cap, C.byref(m)))
         return od[:m.value].copy(), ov[:m.value].copy()
+
+    def h_dot(self, other=None) -> HDot:
+        """<self|H|other> and <self|other> over column 0 of the two engines' vectors (fries_h_dot; calc_h_dot, molecule.cpp:667-885).
+        self is the enumerating side; other=None means the engine itself.  Neither engine may be inside another call on another thread."""
+        r = HdotResult()
+        self._ck(self.lib.fries_h_dot(self.h, (self if other is None else other).h, C.byref(r)))
+        return HDot(r.h, r.ovlp, r.abs_sum, int(r.n_src), int(r.n_terms), int(r.n_hits))
+
+    def variational_energy(self) -> float:
+        """The Rayleigh quotient <v|H|v> / <v|v> of the current vector, on the scale of numer / denom."""
+        r = self.h_dot()
+        return r.h / r.ovlp
 
     def vec_add(self, dets, vals, ini):
         d = np.ascontiguousarray(dets, dtype=np.uint64)

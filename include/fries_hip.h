@@ -292,6 +292,27 @@ int fries_htrial_download(fries_ctx *ctx, uint64_t *dets, double *vals, size_t c
  * (molecule.cpp:448-665): the stored determinants in position order with column 1. */
 int fries_set_spin_parity(fries_ctx *ctx, int spin_parity);
 int fries_h_offdiag_list(fries_ctx *ctx, const uint64_t *dets, const double *vals, size_t n, uint64_t *out_dets, double *out_vals, size_t cap, size_t *n_out);
+/* The replica estimator: <a|H|b> and <a|b> between column 0 of two contexts' solution vectors -- calc_h_dot (FRIES/Hamiltonians/molecule.cpp:667-885:
+ * enumerate H from one vector's columns, look the targets up in the other, add the diagonal) and DistVec::internal_dot for the overlap, as
+ * obs_repl_mol uses them on independent replicas.  h / ovlp needs no trial vector; with a == b (allowed) it is the Rayleigh quotient of the vector.
+ *   ovlp    = sum_i a_i b_i
+ *   h       = sum_i a_i d_i b_i + sum_i sum_{j in exc(i)} a_i m_ij b_j
+ *   abs_sum = the same sum as h over the magnitudes of its terms (a bound for h's rounding error: ~(n_hits + n_src) * 2^-53 * abs_sum)
+ * i runs over the stored determinants of `a` with a non-zero value; d_i is the diagonal element minus the offset of the run (the HF
+ * energy, or what fries_set_ham_shift set), so h / ovlp is on the scale of numer / denom; exc(i) and m_ij are the symmetry-allowed singles
+ * and doubles and their signed elements exactly as fries_h_offdiag_list enumerates them, fries_set_spin_parity included; b_j is looked up in
+ * b's hash table.  n_src = sources visited, n_terms = excitations with a non-zero element, n_hits = those found in b with a non-zero
+ * value.  `a` is the enumerating side: pass the shorter vector there.  Deterministic: no floating-point atomics, two calls on the
+ * same vectors return the same bits.  Nothing of either vector is changed and nothing stays allocated.
+ * Ordering and threads: the kernels run on a's stream after everything b's stream holds at the time of the call, and the call
+ * returns when the result is on the host.  Neither context may be inside another call on another thread while this one runs.
+ * Refused with a message and without a launch: a context without a molecule and a solution vector, a Hubbard-Holstein context, a
+ * context with a communicator, contexts on different devices, or contexts that differ in n_orb, n_elec, irreps, hf_en or spin_parity.
+ * Out of scope: fries_h_dot over ranks (it needs an exchange of the targets), more than one value column per side, Hubbard-Holstein,
+ * replicas for drivers other than frisys_mol_hip, and a binding in include/FRIES (that facade holds one device-bound vector per
+ * process).  fries_frisys_iterate, its launch count and its draws are untouched. */
+typedef struct { double h, ovlp, abs_sum; uint64_t n_src, n_terms, n_hits; } fries_hdot_result;
+int fries_h_dot(fries_ctx *a, fries_ctx *b, fries_hdot_result *out);
 
 /* The hot-path operators one by one, on the context's solution vector. */
 /* apply_HBPP_sys (heat_bathPP.cpp:686-992) with the five uniforms it would draw; outputs as
