@@ -327,3 +327,5 @@ void fr_h_diag_vec(FriesCtx *c, double id_fac, double h_fac);
 uint64_t fr_h_offdiag_vec(FriesCtx *c, double h_fac);
 // hdot.hip
 void fr_h_dot(FriesCtx *a, FriesCtx *b, fries_hdot_result *out);
+// rdm1.hip
+void fr_rdm1(FriesCtx *a, FriesCtx *b, double *gamma, fries_rdm1_result *out);

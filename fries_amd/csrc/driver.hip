@@ -1014,6 +1014,13 @@ extern "C" int fries_h_dot(fries_ctx *a, fries_ctx *b, fries_hdot_result *out) {
     fr_h_dot(&a->c, &b->c, out);
     FR_API_END
 }
+// one_elec_op (molecule.cpp:222-252) for every orbital pair at once, dotted with the other vector: rdm1.hip
+extern "C" int fries_rdm1(fries_ctx *a, fries_ctx *b, double *gamma, fries_rdm1_result *out) {
+    FR_API_BEGIN
+    if (!a || !b || !gamma || !out) throw FriesError("fries_rdm1: null argument");
+    fr_rdm1(&a->c, &b->c, gamma, out);
+    FR_API_END
+}
 
 extern "C" int fries_set_vec_scrambler(fries_ctx *h, const uint32_t *vec_scr, size_t n) {
     FR_API_BEGIN

@@ -13,22 +13,11 @@
 // value is left.  The association order is a function of curr_size alone, so two calls on the same vectors return the same bits.
 #include "ctx.hpp"
 #include "enum_rows.hpp"
+#include "hdot_probe.hpp"       // hd_resolve, shared with k_rdm1
 #include <cstring>
 
 #define HD_ILP 4
 #define HD_CHUNK 4096
-
-// value of determinant d in column 0 of V; 0 for a miss.  e = the slot the first probe returned.
-__device__ __forceinline__ double hd_resolve(const VecDev &V, det_t d, uint32_t s, HSlot e) {
-    const uint32_t mask = V.hcap - 1;
-    for (uint32_t probe = 0; probe < V.hcap; probe++) {
-        if (e.key == d) return e.val < V.cap ? V.v0[e.val] : 0.0;
-        if (e.key == FR_EMPTY_KEY) return 0.0;
-        s = (s + 1) & mask;
-        e = V.hs[s];
-    }
-    return 0.0;
-}
 
 // part: [6][n_pos] as doubles h, ovlp, abs_sum and (in cnt) n_src, n_terms, n_hits of every position
 __global__ void __launch_bounds__(FR_BLOCK) k_hdot(VecDev A, VecDev B, SysDev S, uint32_t n_pos, double *part, unsigned long long *cnt) {

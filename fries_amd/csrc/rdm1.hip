@@ -1,0 +1,196 @@
+// The spin-summed one-body density matrix between the solution vectors of two contexts, gamma[p][q] = <a| sum_sigma c+_{p sigma} c_{q sigma} |b>
+// (what the reference forms one orbital pair at a time: one_elec_op, FRIES/Hamiltonians/molecule.cpp:222-252, then DistVec::internal_dot,
+// as observables_mol and obs_repl_mol do).  Every stored determinant i of `a` with a non-zero value enumerates its same-spin single
+// replacements -- occupied p, empty q, both spins: n_elec * (n_orb - n_elec / 2) of them, no rejection and no symmetry table -- and
+// looks |j> = |i with p emptied and q filled> up in `b`'s hash table; a_i * sign * b_j goes to bin (p, q).  The diagonal is the number
+// operator: a_i * b_i to bin (p, p) for every occupied spin orbital of i.
+//
+// Shape: a workgroup of four waves owns RD_BPOS contiguous positions, a wave RD_WPOS = 64 of them.  The wave loads its 64 sources in one
+// coalesced pass and walks them in order, the source broadcast from the lane that holds it.  The candidates of a source form one index
+// space, each spin padded to a multiple of 64 so that the 64 lanes of a step hold candidates of one spin -- and so 64 different bins.
+// A lane takes RD_ILP candidates per round and issues their first probes (one 16-byte HSlot each) together before it resolves any.
+//
+// Accumulation and determinism: no floating-point atomics anywhere.  Each wave keeps a private n_orb x n_orb matrix in LDS and adds
+// into it by plain read-modify-write: within a step the bins are distinct, and the steps follow each other in program order (alpha
+// before beta, source after source).  The four waves' matrices are added in wave order, the workgroups' matrices by k_rdm1_reduce,
+// RD_FAN of them per workgroup in index order, level by level until one is left.  The order in which every bin's terms are associated is
+// a function of curr_size and the positions alone: two calls on the same vectors return the same bits.
+#include "ctx.hpp"
+#include "hdot_probe.hpp"
+#include "rdm1_plan.hpp"
+#include <cstring>
+
+#ifndef RD_ILP
+#define RD_ILP 4                // probes a lane has in flight per round
+#endif
+#ifndef RD_LDS_ORB
+#define RD_LDS_ORB FR_MAX_ORB   // edge of a wave's matrix in LDS (diagnostic builds: a larger one lowers the occupancy)
+#endif
+
+// orders the LDS read-modify-writes of one step before those of the next (lanes of one wave run in lock-step; LDS serves a wave's
+// accesses in order: what is left to rule out is the compiler moving them)
+__device__ __forceinline__ void rd_step_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// part: [gridDim.x][n_orb^2 + RD_NSCAL] (the matrix, ovlp, abs_sum); cnt: [gridDim.x][RD_NCNT] (n_src, n_terms, n_hits)
+__global__ void __launch_bounds__(FR_BLOCK) k_rdm1(VecDev A, VecDev B, uint32_t n_orb, uint32_t n_pos, double *part, unsigned long long *cnt) {
+    __shared__ double G[4][RD_LDS_ORB * RD_LDS_ORB];
+    __shared__ double shs[4][RD_NSCAL];
+    __shared__ unsigned long long shc[4][RD_NCNT];
+    const unsigned w = threadIdx.x >> 6, lane = fr_lane();
+    const unsigned n2 = n_orb * n_orb;
+    double *g = G[w];
+    for (unsigned k = lane; k < n2; k += FR_WAVE) g[k] = 0.0;
+    rd_step_fence();
+    const size_t mine = (size_t)blockIdx.x * RD_BPOS + (size_t)w * RD_WPOS + lane;
+    unsigned long long my_det = 0; double my_val = 0;
+    if (mine < n_pos) { my_det = A.dets[mine]; my_val = A.v0[mine]; }
+    const det_t lowmask = (1ull << n_orb) - 1ull;       // n_orb <= 32
+    double ov = 0, ab = 0;
+    uint32_t n_src = 0, n_terms = 0, n_hits = 0;
+    for (int s = 0; s < RD_WPOS; s++) {
+        const double av = __shfl(my_val, s);
+        if (av == 0) continue;          // hole, zeroed entry or past the end (uniform over the wave)
+        const det_t det = __shfl(my_det, s);
+        n_src++;
+        // the source itself in b, for the overlap and the diagonal: in flight together with the first round below
+        const uint32_t sl0 = fr_hash_slot(det, B.hcap);
+        const HSlot e0 = B.hs[sl0];
+        const det_t occ0 = det & lowmask, occ1 = (det >> n_orb) & lowmask;
+        const unsigned no0 = __popcll(occ0), no1 = __popcll(occ1);
+        const unsigned nc0 = no0 * (n_orb - no0), nc1 = no1 * (n_orb - no1);
+        const unsigned pad0 = (nc0 + FR_WAVE - 1) & ~(FR_WAVE - 1u), n_idx = pad0 + ((nc1 + FR_WAVE - 1) & ~(FR_WAVE - 1u));
+        for (unsigned c0 = 0; c0 < n_idx; c0 += FR_WAVE * RD_ILP) {
+            det_t nd[RD_ILP]; double sg[RD_ILP]; uint32_t sl[RD_ILP], bin[RD_ILP]; HSlot e[RD_ILP];
+#pragma unroll
+            for (int k = 0; k < RD_ILP; k++) {
+                const unsigned idx = c0 + k * FR_WAVE + lane;
+                const unsigned spin = idx >= pad0, c = spin ? idx - pad0 : idx;
+                sg[k] = 0; nd[k] = det; bin[k] = 0; sl[k] = 0;
+                e[k].key = FR_EMPTY_KEY; e[k].val = FR_NOPOS;
+                if (idx < n_idx && c < (spin ? nc1 : nc0)) {
+                    const det_t occ = spin ? occ1 : occ0, holes = ~occ & lowmask;
+                    const unsigned nh = n_orb - (spin ? no1 : no0);
+                    const unsigned p = fr_nth_bit(occ, c / nh), q = fr_nth_bit(holes, c % nh);
+                    const unsigned P = p + spin * n_orb, Q = q + spin * n_orb;
+                    sg[k] = fr_sing_parity(det, P, Q);
+                    nd[k] = det ^ (1ull << P) ^ (1ull << Q);
+                    bin[k] = p * n_orb + q;
+                    sl[k] = fr_hash_slot(nd[k], B.hcap);
+                    e[k] = B.hs[sl[k]];         // the round's first probes are independent of each other
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < RD_ILP; k++) {
+                if (sg[k] != 0) {
+                    n_terms++;
+                    const double bv = hd_resolve(B, nd[k], sl[k], e[k]);
+                    if (bv != 0) {
+                        const double t = av * sg[k] * bv;
+                        g[bin[k]] += t;         // the 64 candidates of a step have one spin: 64 different bins
+                        ab += fabs(t); n_hits++;
+                    }
+                }
+                rd_step_fence();
+            }
+        }
+        const double t = av * hd_resolve(B, det, sl0, e0);
+        if (t != 0) {
+            if (lane == 0) ov += t;
+            for (int spin = 0; spin < 2; spin++) {
+                if (lane < (spin ? no1 : no0)) { const unsigned p = fr_nth_bit(spin ? occ1 : occ0, lane); g[p * n_orb + p] += t; }
+                rd_step_fence();
+            }
+        }
+    }
+    ab = fr_wave_sum(ab);
+    n_terms = fr_wave_sum_u32(n_terms); n_hits = fr_wave_sum_u32(n_hits);
+    if (lane == 0) { shs[w][0] = ov; shs[w][1] = ab; shc[w][0] = n_src; shc[w][1] = n_terms; shc[w][2] = n_hits; }
+    __syncthreads();
+    // the waves' partials in wave order
+    double *row = part + (size_t)blockIdx.x * (n2 + RD_NSCAL);
+    for (unsigned k = threadIdx.x; k < n2; k += FR_BLOCK) row[k] = ((G[0][k] + G[1][k]) + G[2][k]) + G[3][k];
+    if (threadIdx.x < RD_NSCAL) row[n2 + threadIdx.x] = ((shs[0][threadIdx.x] + shs[1][threadIdx.x]) + shs[2][threadIdx.x]) + shs[3][threadIdx.x];
+    if (threadIdx.x < RD_NCNT) cnt[(size_t)blockIdx.x * RD_NCNT + threadIdx.x] = shc[0][threadIdx.x] + shc[1][threadIdx.x] + shc[2][threadIdx.x] + shc[3][threadIdx.x];
+}
+
+// one level of the fold: workgroup b adds rows [b * RD_FAN, (b + 1) * RD_FAN) of the level below, every element in row order
+__global__ void __launch_bounds__(FR_BLOCK) k_rdm1_reduce(const double *in_d, const unsigned long long *in_c, uint32_t n_in, uint32_t stride, double *out_d, unsigned long long *out_c) {
+    const size_t lo = (size_t)blockIdx.x * RD_FAN, hi = lo + RD_FAN < n_in ? lo + RD_FAN : n_in;
+    for (unsigned k = threadIdx.x; k < stride; k += FR_BLOCK) {
+        double x = in_d[lo * stride + k];
+        for (size_t j = lo + 1; j < hi; j++) x += in_d[j * stride + k];
+        out_d[(size_t)blockIdx.x * stride + k] = x;
+    }
+    if (threadIdx.x < RD_NCNT) {
+        unsigned long long y = 0;
+        for (size_t j = lo; j < hi; j++) y += in_c[j * RD_NCNT + threadIdx.x];
+        out_c[(size_t)blockIdx.x * RD_NCNT + threadIdx.x] = y;
+    }
+}
+
+static const char *rd_not_molecule(const FriesCtx *c) {
+    if (c->hh_mode || c->vec.hh_sites) return "fries_rdm1: a Hubbard-Holstein context has no molecular orbitals (out of scope)";
+    if (!c->d_eris || !c->d_hb) return "fries_rdm1: fries_set_molecule must be called on both contexts first";
+    if (!c->vec.dets || !c->vec.hs) return "fries_rdm1: both contexts need a solution vector (run a setup first)";
+    return nullptr;
+}
+
+void fr_rdm1(FriesCtx *a, FriesCtx *b, double *gamma, fries_rdm1_result *out) {
+    // everything that refuses the call comes before the first launch
+    for (const FriesCtx *c : {a, b}) if (const char *why = rd_not_molecule(c)) throw FriesError(why);
+    for (const FriesCtx *c : {a, b})
+        if (c->use_comm || c->n_ranks > 1) throw FriesError("fries_rdm1: a context with a communicator holds one shard of its vector; the density matrix over ranks is out of scope");
+    if (a->device != b->device) throw FriesError("fries_rdm1: the two contexts are on different devices");
+    if (a->n_orb != b->n_orb || a->n_elec != b->n_elec) throw FriesError("fries_rdm1: the two contexts differ in n_orb or n_elec (different molecules)");
+    if (a->n_orb > FR_MAX_ORB) throw FriesError("fries_rdm1: more than 32 orbitals");
+    if (memcmp(a->h_hb.irrep, b->h_hb.irrep, a->n_orb)) throw FriesError("fries_rdm1: the two contexts differ in their orbital irreps (different molecules)");
+    for (const FriesCtx *c : {a, b})
+        if (c->spin_parity != 0) throw FriesError("fries_rdm1: a context with spin_parity != 0 stores one representative per time-reversal pair; unfolding it is out of scope");
+    FR_HIP(hipSetDevice(a->device));
+    hipStream_t st = a->stream;
+    if (a != b) {
+        // `b` is only read: what its stream has enqueued so far must have run before the probes start
+        struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) hipEventDestroy(e); } } ev;
+        FR_HIP(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
+        FR_HIP(hipEventRecord(ev.e, b->stream));
+        FR_HIP(hipStreamWaitEvent(st, ev.e, 0));
+    }
+    uint32_t n_pos = 0;
+    FR_HIP(hipMemcpyAsync(&n_pos, &a->vec.st->curr_size, 4, hipMemcpyDeviceToHost, st));
+    FR_HIP(hipStreamSynchronize(st));
+    const size_t n2 = (size_t)a->n_orb * a->n_orb;
+    *out = fries_rdm1_result{};
+    std::fill(gamma, gamma + n2, 0.0);
+    if (n_pos == 0) return;
+    if (n_pos > a->vec.cap) throw FriesError("fries_rdm1: the vector's size exceeds its capacity");
+    // the levels of the fold back to back; sized from n_pos and checked against what the device has left before anything is launched
+    const Rdm1Plan plan = fr_rdm1_plan(n_pos, a->n_orb);
+    size_t free_b = 0, total_b = 0;
+    FR_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (plan.bytes() > free_b) {
+        std::ostringstream os;
+        os << "fries_rdm1: the partial matrices of " << n_pos << " positions need " << plan.bytes() << " bytes of device memory, " << free_b << " are free";
+        throw FriesError(os.str());
+    }
+    DevMem tmp;
+    double *d_part = tmp.alloc<double>(plan.total_rows * plan.stride);
+    unsigned long long *d_cnt = tmp.alloc<unsigned long long>(plan.total_rows * RD_NCNT);
+    FR_LAUNCH(a, "k_rdm1", k_rdm1, dim3(plan.rows[0]), dim3(FR_BLOCK), a->vec, b->vec, a->n_orb, n_pos, d_part, d_cnt);
+    size_t off = 0;
+    for (size_t l = 0; l + 1 < plan.rows.size(); l++) {
+        const size_t nxt = off + plan.rows[l];
+        FR_LAUNCH(a, "k_rdm1_reduce", k_rdm1_reduce, dim3(plan.rows[l + 1]), dim3(FR_BLOCK), d_part + off * plan.stride, d_cnt + off * RD_NCNT, plan.rows[l],
+                  (uint32_t)plan.stride, d_part + nxt * plan.stride, d_cnt + nxt * RD_NCNT);
+        off = nxt;
+    }
+    std::vector<double> hd(plan.stride); unsigned long long hc[RD_NCNT];
+    FR_HIP(hipMemcpyAsync(hd.data(), d_part + plan.last_row() * plan.stride, plan.stride * sizeof(double), hipMemcpyDeviceToHost, st));
+    FR_HIP(hipMemcpyAsync(hc, d_cnt + plan.last_row() * RD_NCNT, sizeof(hc), hipMemcpyDeviceToHost, st));
+    FR_HIP(hipStreamSynchronize(st));
+    std::copy(hd.begin(), hd.begin() + n2, gamma);
+    out->ovlp = hd[n2]; out->abs_sum = hd[n2 + 1];
+    out->n_src = hc[0]; out->n_terms = hc[1]; out->n_hits = hc[2];
+}

@@ -4,7 +4,7 @@
 //   frisys_mol_hip --fcidump_path F --point_group D2h --distribution HB_unnorm --vec_nonz N --mat_nonz N --max_dets N
 //                  [--target T] [--initiator I] [--epsilon E] [--max_iter K] [--result_dir DIR/] [--load_dir DIR/]
 //                  [--ini_vec PREFIX] [--trial_vec PREFIX] [--det_space FILE] [--ham_shift E] [--seed S] [--device D]
-//                  [--replicas R [--repl_every K]]
+//                  [--replicas R [--repl_every K] [--repl_rdm1 1]]
 //
 // Host side only: option parsing (argparse there, a loop here), the FCIDUMP reader (parse_fcidump / convert_symm,
 // FRIES/io_utils.cpp:189-318), the text outputs projnum.txt / projden.txt / S.txt / norm.txt / nkept.txt / params.txt
@@ -31,6 +31,9 @@
 //     evaluated for the pairs (0,1), (0,2), ..., (1,2), ... with the shorter vector enumerating (R = 1: the pair (0,0), the vector's
 //     Rayleigh quotient).  One line per evaluation goes to <result_dir>replnum.txt (the h values, comma-separated), replden.txt (the
 //     overlaps) and repliter.txt (the iteration count).  A replica that fails releases the others, and the process returns non-zero.
+//   * --repl_rdm1 1 (needs --replicas): at every meeting, after the fries_h_dot pairs, fries_rdm1 for the same pairs in the same order; one
+//     line per pair goes to <result_dir>replrdm1.txt: the n_orb^2 values of gamma(r, s), r < s, row-major and comma-separated (the shorter
+//     vector enumerates and the matrix is transposed back).  Every other output file is what it is without the flag.
 #include "driver_common.hpp"
 #include <sstream>
 #include <random>
@@ -51,6 +54,7 @@ struct Args {
     uint32_t ranks = 0;                 // --ranks: thread ranks inside this process
     std::vector<int> devices;           // --devices: GPU of every thread rank
     uint32_t replicas = 0, repl_every = 0;      // --replicas / --repl_every: independent runs inside this process and how often they are compared
+    bool repl_rdm1 = false;                     // --repl_rdm1: the one-body density matrix of every pair at every meeting
 };
 
 static Args parse_args(int argc, char **argv) {
@@ -82,6 +86,10 @@ static Args parse_args(int argc, char **argv) {
     if (kv.count("repl_every")) {
         if (!r.replicas) throw std::runtime_error("--repl_every needs --replicas");
         r.repl_every = (uint32_t)std::stoul(kv["repl_every"]);
+    }
+    if (kv.count("repl_rdm1")) {
+        if (!r.replicas) throw std::runtime_error("--repl_rdm1 needs --replicas");
+        r.repl_rdm1 = std::stoul(kv["repl_rdm1"]) != 0;
     }
     if (kv.count("devices")) { std::stringstream ss(kv["devices"]); std::string t; while (std::getline(ss, t, ',')) r.devices.push_back(std::stoi(t)); }
     return r;
@@ -156,16 +164,23 @@ static bool load_last_line(const std::string &path, double *out) {
 // with an exception instead of leaving it at a barrier nobody else will reach.
 struct Replicas {
     const int R, precision;
+    const bool want_rdm1;
+    uint32_t n_orb = 0;
     std::vector<fries_ctx *> ctx;
-    std::ofstream num_file, den_file, iter_file;
+    std::ofstream num_file, den_file, iter_file, rdm1_file;
     std::mutex mu;
     std::condition_variable cv;
     int arrived = 0; uint64_t generation = 0; bool aborted = false;
-    Replicas(int R_, const Args &args) : R(R_), precision(args.precision), ctx((size_t)R_, nullptr) {
+    Replicas(int R_, const Args &args, uint32_t n_orb_) : R(R_), precision(args.precision), want_rdm1(args.repl_rdm1), n_orb(n_orb_), ctx((size_t)R_, nullptr) {
         const std::string &rd = args.result_dir;
         num_file.open(rd + "replnum.txt", std::ofstream::app); den_file.open(rd + "replden.txt", std::ofstream::app); iter_file.open(rd + "repliter.txt", std::ofstream::app);
         if (!num_file.is_open() || !den_file.is_open() || !iter_file.is_open()) throw std::runtime_error("Could not open file for writing in directory " + rd);
         num_file.precision(precision); den_file.precision(precision);
+        if (want_rdm1) {
+            rdm1_file.open(rd + "replrdm1.txt", std::ofstream::app);
+            if (!rdm1_file.is_open()) throw std::runtime_error("Could not open file for writing in directory " + rd);
+            rdm1_file.precision(precision);
+        }
     }
     void abort() { std::lock_guard<std::mutex> lk(mu); aborted = true; cv.notify_all(); }
     // fries_h_dot for every pair, the shorter vector enumerating (the estimate is symmetric up to rounding)
@@ -185,6 +200,23 @@ struct Replicas {
         for (int r = 0; r < R; r++) for (int s = r + 1; s < R; s++) one(r, s);
         num_file << '\n'; den_file << '\n'; iter_file << iters_done << '\n';
         num_file.flush(); den_file.flush(); iter_file.flush();
+        if (!want_rdm1) return;
+        // fries_rdm1 for the same pairs in the same order: gamma(r, s), the shorter vector enumerating and the matrix transposed back
+        std::vector<double> g((size_t)n_orb * n_orb);
+        auto one_rdm1 = [&](int r, int s) {
+            const bool swap = nz[r] > nz[s];
+            fries_rdm1_result res;
+            ck(fries_rdm1(ctx[swap ? s : r], ctx[swap ? r : s], g.data(), &res));
+            for (uint32_t p = 0; p < n_orb; p++)
+                for (uint32_t q = 0; q < n_orb; q++) {
+                    if (p || q) rdm1_file << ',';
+                    rdm1_file << (swap ? g[(size_t)q * n_orb + p] : g[(size_t)p * n_orb + q]);
+                }
+            rdm1_file << '\n';
+        };
+        if (R == 1) one_rdm1(0, 0);
+        for (int r = 0; r < R; r++) for (int s = r + 1; s < R; s++) one_rdm1(r, s);
+        rdm1_file.flush();
     }
     void meet(uint32_t iters_done) {
         std::unique_lock<std::mutex> lk(mu);
@@ -327,7 +359,7 @@ int main(int argc, char **argv) {
         if (args.replicas) {
             // R independent one-rank runs = R threads of this process, started like the --ranks threads below
             const int R = (int)args.replicas;
-            Replicas repl(R, args);
+            Replicas repl(R, args, in.n_orb);
             std::vector<std::string> errs((size_t)R);
             std::vector<std::thread> th;
             for (int r = 0; r < R; r++)

@@ -29,7 +29,7 @@ EXPORTS = [
     "fries_set_proc_scrambler", "fries_tie_margins", "fries_measure_copy_bandwidth", "fries_piv_stats", "fries_set_trial_vector", "fries_set_initial_vector", "fries_set_ham_shift", "fries_vec_add_to", "fries_death_clone", "fries_dots", "fries_find_preserve", "fries_sys_comp",
     "fries_vec_column_download", "fries_vec_column_upload", "fries_vec_column_zero", "fries_vec_diag_download", "fries_vec_dot_list", "fries_vec_add_vecs", "fries_set_det_space", "fries_vec_set_dense", "fries_dense_sizes", "fries_hostcomm_create", "fries_set_vec_scrambler", "fries_hh_comp_sub", "fries_hh_ref_ovlp", "fries_set_spin_parity", "fries_h_offdiag_list",
     "fries_spawn_from_comp", "fries_dense_apply", "fries_dense_norm", "fries_dense_h_count", "fries_comp_download",
-    "fries_h_dot",
+    "fries_h_dot", "fries_rdm1",
 ]
 
 
@@ -91,6 +91,38 @@ class HDot(NamedTuple):
     @property
     def energy(self) -> float:
         return self.h / self.ovlp
+
+
+class Rdm1Result(C.Structure):
+    """struct fries_rdm1_result"""
+    _fields_ = [("ovlp", C.c_double), ("abs_sum", C.c_double), ("n_src", C.c_uint64), ("n_terms", C.c_uint64), ("n_hits", C.c_uint64)]
+
+
+class Rdm1(NamedTuple):
+    """fries_rdm1's result: gamma[p, q] = <a| sum_sigma c+_{p sigma} c_{q sigma} |b> (an [n_orb, n_orb] array, the number operator on the
+    diagonal), ovlp = <a|b>, abs_sum = the sum of the magnitudes of the off-diagonal terms; the counts of sources, probes and probes
+    that found a non-zero value in b."""
+    gamma: np.ndarray
+    ovlp: float
+    abs_sum: float
+    n_src: int
+    n_terms: int
+    n_hits: int
+
+    def expectation(self, op) -> float:
+        """<a| O |b> / <a|b> of the one-electron operator with the [n_orb, n_orb] matrix op[p, q] = <p|o|q>."""
+        op = np.asarray(op, dtype=np.float64)
+        if op.shape != self.gamma.shape:
+            raise ValueError(f"the operator matrix must have shape {self.gamma.shape}")
+        return float(np.sum(op * self.gamma) / self.ovlp)
+
+    def natural_occupations(self) -> np.ndarray:
+        """Eigenvalues of the symmetrised, normalised density matrix (gamma + gamma.T) / (2 ovlp), descending."""
+        return np.linalg.eigvalsh((self.gamma + self.gamma.T) / (2.0 * self.ovlp))[::-1].copy()
+
+    def transposed(self) -> "Rdm1":
+        """gamma(b, a) from gamma(a, b): the matrix transposed, everything else as it is."""
+        return self._replace(gamma=np.ascontiguousarray(self.gamma.T))
 
 
 ITERLOG_DTYPE = np.dtype([("numer", "f8"), ("denom", "f8"), ("shift", "f8"), ("norm", "f8"), ("nkept", "u4"), ("n_nonz", "i4"),
@@ -193,6 +225,7 @@ def load_library() -> C.CDLL:
     lib.fries_dense_h_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     lib.fries_comp_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.fries_h_dot.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(HdotResult)]
+    lib.fries_rdm1.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Rdm1Result)]
     _lib = lib
     return lib
 
@@ -530,6 +563,16 @@ class FriEngine:
         r = HdotResult()
         self._ck(self.lib.fries_h_dot(self.h, (self if other is None else other).h, C.byref(r)))
         return HDot(r.h, r.ovlp, r.abs_sum, int(r.n_src), int(r.n_terms), int(r.n_hits))
+
+    def rdm1(self, other=None) -> Rdm1:
+        """The one-body density matrix <self| sum_sigma c+_{p sigma} c_{q sigma} |other> over column 0 of the two engines' vectors
+        (fries_rdm1; one_elec_op, molecule.cpp:222-252, for every orbital pair at once).  self is the enumerating side; other=None
+        means the engine itself.  Neither engine may be inside another call on another thread."""
+        n = self.mol.n_orb if self.mol is not None else 0
+        g = np.zeros((max(n, 1), max(n, 1)))        # (a context without a molecule is refused by the call itself)
+        r = Rdm1Result()
+        self._ck(self.lib.fries_rdm1(self.h, (self if other is None else other).h, _ptr(g), C.byref(r)))
+        return Rdm1(g, r.ovlp, r.abs_sum, int(r.n_src), int(r.n_terms), int(r.n_hits))
 
     def variational_energy(self) -> float:
         """The Rayleigh quotient <v|H|v> / <v|v> of the current vector, on the scale of numer / denom."""

@@ -313,6 +313,30 @@ int fries_h_offdiag_list(fries_ctx *ctx, const uint64_t *dets, const double *val
  * process).  fries_frisys_iterate, its launch count and its draws are untouched. */
 typedef struct { double h, ovlp, abs_sum; uint64_t n_src, n_terms, n_hits; } fries_hdot_result;
 int fries_h_dot(fries_ctx *a, fries_ctx *b, fries_hdot_result *out);
+/* The one-body density matrix between two replicas: gamma[p * n_orb + q] = <a| sum_sigma c+_{p sigma} c_{q sigma} |b> over column 0 of the two
+ * contexts' solution vectors, all n_orb * n_orb orbital pairs in one pass.  For p != q it is what the reference forms for ONE pair per run
+ * -- one_elec_op(vec, n_orb, des = q, cre = p, 2) (FRIES/Hamiltonians/molecule.cpp:222-252) with column 0 holding b and column 1 holding a,
+ * then DistVec::internal_dot(1, 2), as observables_mol and obs_repl_mol do: the sum over both spins of a_i * sign * b_j, where |i> is |j>
+ * with spin orbital q sigma emptied and p sigma filled and sign = (-1)^(occupied spin orbitals strictly between them) (sing_det_parity).
+ * The diagonal is the number operator, gamma[p][p] = sum_i a_i b_i (n_{p alpha}(i) + n_{p beta}(i)): one_elec_op itself yields nothing for
+ * des == cre (its test read_bit(des) && !read_bit(cre) cannot hold), and the occupation is the meaningful diagonal.  Hence
+ * trace(gamma) = n_elec * <a|b>, gamma(a, b)[p][q] = gamma(b, a)[q][p], and every one-electron expectation value is sum(op * gamma) / ovlp.
+ *   ovlp    = <a|b> = sum_i a_i b_i
+ *   abs_sum = the sum of the magnitudes of all off-diagonal terms
+ *   n_src   = stored determinants of `a` with a non-zero value; n_terms = probes issued = n_src * n_elec * (n_orb - n_elec / 2);
+ *   n_hits  = probes that found a non-zero value in b
+ * No symmetry is consulted: a bin whose orbitals differ in irrep is the sum of whatever the vectors hold.
+ * As in fries_h_dot: `a` enumerates and `b` is only probed (pass the shorter vector as `a` and transpose); neither vector, diagonal cache
+ * nor host mirror changes; a == b is allowed; the kernels run on a's stream after everything b's stream holds at the time of the call, the
+ * call returns when the result is on the host, and neither context may be inside another call on another thread meanwhile.  Deterministic:
+ * no floating-point atomics, two calls on the same vectors return the same bits in every bin.  Nothing stays allocated.
+ * Refused with a message and without a launch: a null argument, a context without a molecule or without a solution vector, a
+ * Hubbard-Holstein context, a context with a communicator, contexts on different devices or that differ in n_orb, n_elec or irreps, and
+ * spin_parity != 0 on either side (a time-reversal vector stores one representative per pair).  hf_en plays no part and is not compared.
+ * Out of scope: fries_rdm1 over ranks, time-reversal vectors, Hubbard-Holstein, two-body density matrices, the importance-weighted
+ * compression of observables_mol (weight_vec, --exponent), a binding in include/FRIES, and replicas for drivers other than frisys_mol_hip. */
+typedef struct { double ovlp, abs_sum; uint64_t n_src, n_terms, n_hits; } fries_rdm1_result;
+int fries_rdm1(fries_ctx *a, fries_ctx *b, double *gamma /* n_orb * n_orb, row-major */, fries_rdm1_result *out);
 
 /* The hot-path operators one by one, on the context's solution vector. */
 /* apply_HBPP_sys (heat_bathPP.cpp:686-992) with the five uniforms it would draw; outputs as
