@@ -8,9 +8,8 @@
 //     ranks may share a GPU -- RCCL refuses that).  Device-to-device copies between the ranks' staging buffers with a
 //     host barrier on both sides.  This is what the multi-rank parity tests use on a one-GPU box (8 ranks of BASELINE
 //     config 4), and it lets one process drive several GPUs.
-#include "ctx.hpp"
+#include "api.hpp"
 #include <rccl/rccl.h>
-#include <cstring>
 #include <condition_variable>
 #include <mutex>
 #include <atomic>

@@ -13,8 +13,6 @@
 
 struct FriesError : std::runtime_error { using std::runtime_error::runtime_error; };
 
-void fr_set_error(const std::string &msg);
-
 #define FR_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { throw FriesError(std::string(#call) + ": " + hipGetErrorString(e_)); } } while (0)
 
 #include "devmem.hpp"
@@ -24,8 +22,9 @@ static inline unsigned fr_blocks(size_t n, size_t per) { return (unsigned)((n + 
 struct ProfSpan { const char *name; hipEvent_t a, b; };
 struct ProfAgg { std::string name; double ms; uint64_t calls; };
 struct FriesCtx;
-void fr_prof_begin(FriesCtx *c, const char *name);
+void fr_prof_begin(FriesCtx *c, const char *name);        // frisys.hip
 void fr_prof_end(FriesCtx *c);
+void fr_prof_collect(FriesCtx *c);
 #define FR_LAUNCH(c, name, kern, grid, block, ...) do { \
     if ((c)->prof_on) fr_prof_begin((c), name); \
     hipLaunchKernelGGL(kern, grid, block, 0, (c)->stream, __VA_ARGS__); \
@@ -111,9 +110,6 @@ struct fries_comm_ops {
     int (*allgather)(void *, uint64_t, void *);
     int (*alltoallv)(void *, const uint64_t *, const uint64_t *, void *);
 };
-struct FriesCtx;
-// gathers c->comm.small_send[0, bytes) of every rank; returns the device address of the rank-ordered blocks
-const void *fr_allgather(FriesCtx *c, size_t bytes);
 
 // FCIQMC work arrays (fciqmc.hip): per stored determinant and per spawning attempt
 struct FqWork {
@@ -257,6 +253,13 @@ struct FriesCtx {
     std::vector<ProfAgg> prof_agg;
 };
 
+// the system as the kernels take it: the one place that fills a SysDev
+static inline SysDev fr_sysdev(const FriesCtx *c) {
+    SysDev S;
+    S.n_orb = c->n_orb; S.n_elec = c->n_elec; S.h_core = c->d_h; S.eris = c->d_eris; S.hb = c->d_hb; S.hf_en = c->hf_en; S.spin_parity = c->spin_parity;
+    return S;
+}
+
 // vec.hip
 void fr_vec_alloc(FriesCtx *c, DevMem &m, VecDev *v, uint32_t cap);       // the alloc functions take the owner they allocate from: c->mem, or a caller's scoped DevMem
 void fr_vec_sync_state(FriesCtx *c, VecDev *v, VecState *out);
@@ -267,16 +270,42 @@ void fr_vec_reserve_hash(FriesCtx *c, VecDev *v, uint32_t n_new);
 void fr_spawn_alloc(FriesCtx *c, DevMem &m, uint32_t cap);
 void fr_xch_alloc(FriesCtx *c, DevMem &m, uint32_t cap);
 uint32_t fr_spawn_exchange(FriesCtx *c, uint32_t n_local, int one_pass = 0, bool *merged = nullptr);      // 0: two passes (frisys_mol); 1: one pass, flag inside an integer value; 2: one pass, flag in bit 63 of the index
-// driver.hip: host steps the drivers share
+// enqueue a copy of `bytes` (a multiple of 4, <= 2 KB) at device address src into the readback block; -> host address to read AFTER the next
+// synchronisation of the stream.  The block is a ring: a slot stays valid until ~RB_BYTES more have been asked for.
+const void *fr_readback(FriesCtx *c, const void *src, size_t bytes, bool held = false, uint32_t *ticket = nullptr);      // ticket != nullptr: the copy raises a ticket itself (fr_stream_wait_ticket)
+uint32_t fr_ticket_reserve(FriesCtx *c);
+// Waits until everything enqueued on the context's stream so far has run: a one-thread kernel stores a ticket into host-coherent pinned
+// memory and the host polls that word.  (hipStreamSynchronize returns ~20 us after the stream has drained; the iteration has about a
+// dozen such waits, during each of which the GPU idles.)
+void fr_stream_wait(FriesCtx *c);
+uint32_t fr_stream_ticket(FriesCtx *c);
+void fr_stream_wait_ticket(FriesCtx *c, uint32_t t);
+void fr_rb_init(FriesCtx *c, DevMem &m);
+// frisys.hip: host steps the drivers share, the frisys_mol and frifull_mol loops, and the three pieces of the frisys_mol iteration that the stepwise entry points call too
+const void *fr_allgather(FriesCtx *c, size_t bytes);       // gathers c->comm.small_send[0, bytes) of every rank; returns the device address of the rank-ordered blocks
+int fr_host_idx_to_proc(const FriesCtx *c, det_t d);
 void fr_spawn_upload_merge(FriesCtx *c, const det_t *det, const double *val, const uint8_t *ini, uint32_t m, bool same_column);
 void fr_spawn_reference_det(FriesCtx *c);
 void fr_driver_prologue(FriesCtx *c, uint32_t seed, bool take_proc_scr, bool take_vec_scr, uint32_t adder_cap);
 void fr_adjust_shift(FriesCtx *c, double glob_norm);
 uint32_t fr_log_err(FriesCtx *c);
+void fr_log_fill(FriesCtx *c, fries_iter_log *lg, int n_comp_len);
+void fr_check_dev_err(FriesCtx *c);
+void fr_dense_declare(FriesCtx *c, uint32_t n, bool zero);
+void fr_frisys_setup(FriesCtx *c, const fries_frisys_params *p);
+void fr_frisys_iterate(FriesCtx *c, fries_iter_log *lg);
+void fr_frifull_setup(FriesCtx *c, const fries_frifull_params *p);
+void fr_frifull_iterate(FriesCtx *c, fries_iter_log *lg);
+uint32_t fr_spawn_comp_result(FriesCtx *c, double eps, double init_thresh);
+uint32_t fr_dense_multiply(FriesCtx *c);
+double fr_dense_norm_all(FriesCtx *c);
 // hbpp.hip
 void fr_hbpp_alloc(FriesCtx *c, DevMem &m, uint32_t cap);
 void fr_hbpp_apply(FriesCtx *c, uint32_t n_samp, const double rn[5]);
-void fr_spawn_from_comp(FriesCtx *c);
+void fr_hbpp_apply_unit(FriesCtx *c, uint32_t n_samp, const double rn[5]);
+void fr_hbpp_piv_apply(FriesCtx *c, uint32_t n_samp, int unit_matrel, uint32_t stage_len[5]);
+void fr_hh_apply(FriesCtx *c, uint32_t n_samp, const double rn[2]);
+void fr_hh_stage(FriesCtx *c, int stage, uint32_t n_samp, double rn);
 // compress.hip
 void fr_vcomp_alloc(FriesCtx *c, DevMem &m, uint32_t cap);
 void fr_death_clone(FriesCtx *c, uint32_t vec_size_before);
@@ -287,41 +316,28 @@ void fr_dots(FriesCtx *c, double *numer, double *denom);
 const void *fr_dots_enqueue(FriesCtx *c);
 void fr_dots_collect(FriesCtx *c, const void *h_d, double *numer, double *denom);
 void fr_unkept_norm(FriesCtx *c, uint32_t bound);
+double fr_abs_norm(FriesCtx *c);
+void fr_multi_walks(FriesCtx *c, double rn, double prev_glob_norm, uint32_t n_teeth, uint32_t *n_walk, double *unit_out);
 // pivotal.hip
 void fr_piv_flat_reserve(FriesCtx *c, DevMem &m, uint32_t cap);
 void fr_piv_comp_flat(FriesCtx *c, uint32_t n, uint32_t compress_size);
-void fr_hbpp_piv_apply(FriesCtx *c, uint32_t n_samp, int unit_matrel, uint32_t stage_len[5]);
 void fr_piv_comp(FriesCtx *c, uint32_t compress_size, uint32_t *n_kept, double *glob_norm);
 void fr_test_piv_adjust(FriesCtx *c, uint32_t *n_loc_io, double exp_loc, uint32_t n_tot, double tot_norm, double *new_norm, uint8_t *flags_out);
 // fciqmc.hip
 void fr_fq_setup(FriesCtx *c, const fries_fciqmc_params *p);
 void fr_fq_iterate(FriesCtx *c, fries_fciqmc_log *lg);
-// hh.hip
 void fr_multi_setup(FriesCtx *c, const fries_frimulti_params *p);
 void fr_multi_iterate(FriesCtx *c, fries_fciqmc_log *lg);
-double fr_abs_norm(FriesCtx *c);
-void fr_multi_walks(FriesCtx *c, double rn, double prev_glob_norm, uint32_t n_teeth, uint32_t *n_walk, double *unit_out);
+// hh.hip
 void fr_hh_setup(FriesCtx *c, const fries_hh_params *p);
 void fr_hh_iterate(FriesCtx *c, fries_iter_log *lg);
-void fr_hh_apply(FriesCtx *c, uint32_t n_samp, const double rn[2]);
 void fr_hh_clear_pos0(FriesCtx *c);
-void fr_hh_stage(FriesCtx *c, int stage, uint32_t n_samp, double rn);
 void fr_hh_ref_ovlp(FriesCtx *c, double out[3]);
-int fr_host_idx_to_proc(const FriesCtx *c, det_t d);
 // system.hip
-void fr_dense_h_setup(FriesCtx *c, DevMem &m);
-// enqueue a copy of `bytes` (a multiple of 4, <= 2 KB) at device address src into the readback block; -> host address to read AFTER the next
-// synchronisation of the stream.  The block is a ring: a slot stays valid until ~RB_BYTES more have been asked for.  (vec.hip)
-const void *fr_readback(FriesCtx *c, const void *src, size_t bytes, bool held = false, uint32_t *ticket = nullptr);      // ticket != nullptr: the copy raises a ticket itself (fr_stream_wait_ticket)
-uint32_t fr_ticket_reserve(FriesCtx *c);
-// Waits until everything enqueued on the context's stream so far has run: a one-thread kernel stores a ticket into host-coherent pinned
-// memory and the host polls that word.  (hipStreamSynchronize returns ~20 us after the stream has drained; the iteration has about a
-// dozen such waits, during each of which the GPU idles.)
-void fr_stream_wait(FriesCtx *c);
-uint32_t fr_stream_ticket(FriesCtx *c);
-void fr_stream_wait_ticket(FriesCtx *c, uint32_t t);
-void fr_rb_init(FriesCtx *c, DevMem &m);
 void fr_system_upload(FriesCtx *c, uint32_t n_orb, uint32_t n_elec, const uint8_t *irreps, const double *h_core, const double *eris);
+void fr_dense_h_setup(FriesCtx *c, DevMem &m);
+void fr_h_apply_list(FriesCtx *c, const std::vector<det_t> &src, const std::vector<double> &val,
+                     std::vector<det_t> &out_det, std::vector<double> &out_val, uint32_t *n_sing0, uint32_t *n_doub0, bool with_diag = true);
 void fr_h_trial_setup(FriesCtx *c);
 void fr_h_diag_vec(FriesCtx *c, double id_fac, double h_fac);
 uint64_t fr_h_offdiag_vec(FriesCtx *c, double h_fac);

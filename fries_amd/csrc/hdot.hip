@@ -14,7 +14,7 @@
 #include "ctx.hpp"
 #include "enum_rows.hpp"
 #include "hdot_probe.hpp"       // hd_resolve, shared with k_rdm1
-#include <cstring>
+#include "pair_frame.hpp"
 
 #define HD_ILP 4
 #define HD_CHUNK 4096
@@ -99,39 +99,14 @@ __global__ void __launch_bounds__(FR_BLOCK) k_hdot_reduce(const double *in_d, co
     }
 }
 
-static const char *hd_not_molecule(const FriesCtx *c) {
-    if (c->hh_mode || c->vec.hh_sites) return "fries_h_dot: a Hubbard-Holstein context has no molecular Hamiltonian (out of scope)";
-    if (!c->d_eris || !c->d_hb) return "fries_h_dot: fries_set_molecule must be called on both contexts first";
-    if (!c->vec.dets || !c->vec.hs) return "fries_h_dot: both contexts need a solution vector (run a setup first)";
-    return nullptr;
-}
-
 void fr_h_dot(FriesCtx *a, FriesCtx *b, fries_hdot_result *out) {
-    // everything that refuses the call comes before the first launch
-    for (const FriesCtx *c : {a, b}) if (const char *why = hd_not_molecule(c)) throw FriesError(why);
-    for (const FriesCtx *c : {a, b})
-        if (c->use_comm || c->n_ranks > 1) throw FriesError("fries_h_dot: a context with a communicator holds one shard of its vector; the estimator over ranks is out of scope");
-    if (a->device != b->device) throw FriesError("fries_h_dot: the two contexts are on different devices");
-    if (a->n_orb != b->n_orb || a->n_elec != b->n_elec) throw FriesError("fries_h_dot: the two contexts differ in n_orb or n_elec (different molecules)");
-    if (memcmp(a->h_hb.irrep, b->h_hb.irrep, a->n_orb)) throw FriesError("fries_h_dot: the two contexts differ in their orbital irreps (different molecules)");
+    const uint32_t n_pos = fr_pair_begin("fries_h_dot", a, b);
     if (a->hf_en != b->hf_en) throw FriesError("fries_h_dot: the two contexts differ in hf_en, the offset of the diagonal (different molecules or --ham_shift)");
     if (a->spin_parity != b->spin_parity) throw FriesError("fries_h_dot: the two contexts differ in spin_parity");
-    FR_HIP(hipSetDevice(a->device));
     hipStream_t st = a->stream;
-    if (a != b) {
-        // `b` is only read: what its stream has enqueued so far must have run before the probes start
-        struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) hipEventDestroy(e); } } ev;
-        FR_HIP(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
-        FR_HIP(hipEventRecord(ev.e, b->stream));
-        FR_HIP(hipStreamWaitEvent(st, ev.e, 0));
-    }
-    uint32_t n_pos = 0;
-    FR_HIP(hipMemcpyAsync(&n_pos, &a->vec.st->curr_size, 4, hipMemcpyDeviceToHost, st));
-    FR_HIP(hipStreamSynchronize(st));
     *out = fries_hdot_result{};
     if (n_pos == 0) return;
-    if (n_pos > a->vec.cap) throw FriesError("fries_h_dot: the vector's size exceeds its capacity");
-    SysDev S; S.n_orb = a->n_orb; S.n_elec = a->n_elec; S.h_core = a->d_h; S.eris = a->d_eris; S.hb = a->d_hb; S.hf_en = a->hf_en; S.spin_parity = a->spin_parity;
+    const SysDev S = fr_sysdev(a);
     // the levels of the tree back to back: [3][n_pos], [3][ceil(n_pos / HD_CHUNK)], ... down to [3][1]
     size_t total = n_pos;
     for (uint32_t n = n_pos;;) { n = fr_blocks(n, HD_CHUNK); total += n; if (n <= 1) break; }

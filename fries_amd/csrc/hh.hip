@@ -408,11 +408,7 @@ void fr_hh_iterate(FriesCtx *c, fries_iter_log *lg) {
     c->tot_iters++; c->tot_spawns += c->num_success;
     if (lg) {
         fr_vec_sync_state(c, &c->vec, &c->h_vst);
-        lg->numer = c->numer; lg->denom = c->denom; lg->shift = c->en_shift; lg->norm = c->glob_norm;
-        lg->nkept = c->nkept; lg->n_nonz = c->h_vst.n_nonz; lg->curr_size = c->h_vst.curr_size;
-        lg->num_success = c->num_success;
-        for (int k = 0; k < 5; k++) lg->comp_len[k] = k < 2 ? c->comp_len[k] : 0;
-        lg->err = fr_log_err(c);
+        fr_log_fill(c, lg, 2);
     }
 }
 

@@ -398,7 +398,6 @@ __global__ void __launch_bounds__(FR_BLOCK) k_piv_tail(VecDev V, VcompBuf B, Piv
     else B.keep[i] = 0;
 }
 
-void fr_unkept_norm(FriesCtx *c, uint32_t bound);      // compress.hip
 
 // piv_samp_serial (compress_utils.cpp:389-518) on the host, for the handful of fractional rank weights piv_budget samples
 // from (one per rank): the same sequence of operations on plain arrays.

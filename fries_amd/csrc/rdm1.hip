@@ -18,7 +18,7 @@
 #include "ctx.hpp"
 #include "hdot_probe.hpp"
 #include "rdm1_plan.hpp"
-#include <cstring>
+#include "pair_frame.hpp"
 
 #ifndef RD_ILP
 #define RD_ILP 4                // probes a lane has in flight per round
@@ -131,41 +131,16 @@ __global__ void __launch_bounds__(FR_BLOCK) k_rdm1_reduce(const double *in_d, co
     }
 }
 
-static const char *rd_not_molecule(const FriesCtx *c) {
-    if (c->hh_mode || c->vec.hh_sites) return "fries_rdm1: a Hubbard-Holstein context has no molecular orbitals (out of scope)";
-    if (!c->d_eris || !c->d_hb) return "fries_rdm1: fries_set_molecule must be called on both contexts first";
-    if (!c->vec.dets || !c->vec.hs) return "fries_rdm1: both contexts need a solution vector (run a setup first)";
-    return nullptr;
-}
-
 void fr_rdm1(FriesCtx *a, FriesCtx *b, double *gamma, fries_rdm1_result *out) {
-    // everything that refuses the call comes before the first launch
-    for (const FriesCtx *c : {a, b}) if (const char *why = rd_not_molecule(c)) throw FriesError(why);
-    for (const FriesCtx *c : {a, b})
-        if (c->use_comm || c->n_ranks > 1) throw FriesError("fries_rdm1: a context with a communicator holds one shard of its vector; the density matrix over ranks is out of scope");
-    if (a->device != b->device) throw FriesError("fries_rdm1: the two contexts are on different devices");
-    if (a->n_orb != b->n_orb || a->n_elec != b->n_elec) throw FriesError("fries_rdm1: the two contexts differ in n_orb or n_elec (different molecules)");
+    const uint32_t n_pos = fr_pair_begin("fries_rdm1", a, b);
     if (a->n_orb > FR_MAX_ORB) throw FriesError("fries_rdm1: more than 32 orbitals");
-    if (memcmp(a->h_hb.irrep, b->h_hb.irrep, a->n_orb)) throw FriesError("fries_rdm1: the two contexts differ in their orbital irreps (different molecules)");
     for (const FriesCtx *c : {a, b})
         if (c->spin_parity != 0) throw FriesError("fries_rdm1: a context with spin_parity != 0 stores one representative per time-reversal pair; unfolding it is out of scope");
-    FR_HIP(hipSetDevice(a->device));
     hipStream_t st = a->stream;
-    if (a != b) {
-        // `b` is only read: what its stream has enqueued so far must have run before the probes start
-        struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) hipEventDestroy(e); } } ev;
-        FR_HIP(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
-        FR_HIP(hipEventRecord(ev.e, b->stream));
-        FR_HIP(hipStreamWaitEvent(st, ev.e, 0));
-    }
-    uint32_t n_pos = 0;
-    FR_HIP(hipMemcpyAsync(&n_pos, &a->vec.st->curr_size, 4, hipMemcpyDeviceToHost, st));
-    FR_HIP(hipStreamSynchronize(st));
     const size_t n2 = (size_t)a->n_orb * a->n_orb;
     *out = fries_rdm1_result{};
     std::fill(gamma, gamma + n2, 0.0);
     if (n_pos == 0) return;
-    if (n_pos > a->vec.cap) throw FriesError("fries_rdm1: the vector's size exceeds its capacity");
     // the levels of the fold back to back; sized from n_pos and checked against what the device has left before anything is launched
     const Rdm1Plan plan = fr_rdm1_plan(n_pos, a->n_orb);
     size_t free_b = 0, total_b = 0;

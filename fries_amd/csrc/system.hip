@@ -137,7 +137,7 @@ void fr_dense_h_setup(FriesCtx *c, DevMem &m) {
     c->n_dense_h = c->n_dense_h_nz = 0;
     if (!c->d_dense_norm) c->d_dense_norm = m.alloc<double>(1);
     if (!ns) return;
-    SysDev S; S.n_orb = c->n_orb; S.n_elec = c->n_elec; S.h_core = c->d_h; S.eris = c->d_eris; S.hb = c->d_hb; S.hf_en = c->hf_en; S.spin_parity = c->spin_parity;
+    const SysDev S = fr_sysdev(c);
     std::vector<double> ones(ns, 1.0);
     DevMem tmp;
     double *d_val = tmp.alloc<double>(ns);
@@ -174,7 +174,7 @@ void fr_h_apply_list(FriesCtx *c, const std::vector<det_t> &src, const std::vect
                      std::vector<det_t> &out_det, std::vector<double> &out_val, uint32_t *n_sing0, uint32_t *n_doub0, bool with_diag) {
     hipStream_t st = c->stream;
     uint32_t ns = (uint32_t)src.size();
-    SysDev S; S.n_orb = c->n_orb; S.n_elec = c->n_elec; S.h_core = c->d_h; S.eris = c->d_eris; S.hb = c->d_hb; S.hf_en = c->hf_en; S.spin_parity = c->spin_parity;
+    const SysDev S = fr_sysdev(c);
     DevMem tmp;      // everything below is this call's own, the temporary vector and spawn buffers included
     det_t *d_src = tmp.alloc<det_t>(ns); double *d_val = tmp.alloc<double>(ns);
     uint32_t *d_cnt = tmp.alloc<uint32_t>(2 * ns), *d_nz = tmp.alloc<uint32_t>(2 * ns), *d_off = tmp.alloc<uint32_t>(2 * ns);
@@ -294,7 +294,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_hop_diag(VecDev V, SysDev S, doubl
     V.v1[i] = o;
 }
 void fr_h_diag_vec(FriesCtx *c, double id_fac, double h_fac) {
-    SysDev S; S.n_orb = c->n_orb; S.n_elec = c->n_elec; S.h_core = c->d_h; S.eris = c->d_eris; S.hb = c->d_hb; S.hf_en = c->hf_en; S.spin_parity = c->spin_parity;
+    const SysDev S = fr_sysdev(c);
     uint32_t bound = c->h_vst.curr_size ? c->h_vst.curr_size : 1;
     FR_LAUNCH(c, "k_hop_diag", k_hop_diag, dim3(fr_blocks(bound, FR_BLOCK)), dim3(FR_BLOCK), c->vec, S, id_fac, h_fac);
 }
@@ -346,7 +346,7 @@ static uint64_t fr_h_offdiag_vec_ranks(FriesCtx *c, double h_fac) {
     hipStream_t st = c->stream;
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     const uint32_t ns = c->h_vst.curr_size;
-    SysDev S; S.n_orb = c->n_orb; S.n_elec = c->n_elec; S.h_core = c->d_h; S.eris = c->d_eris; S.hb = c->d_hb; S.hf_en = c->hf_en; S.spin_parity = c->spin_parity;
+    const SysDev S = fr_sysdev(c);
     if (c->full_cap < ns || !c->full_cnt) full_reserve(c);
     uint32_t nl = 0;
     if (ns) {
@@ -396,7 +396,7 @@ uint64_t fr_h_offdiag_vec(FriesCtx *c, double h_fac) {
     fr_vec_sync_state(c, &c->vec, &c->h_vst);
     const uint32_t ns = c->h_vst.curr_size;
     if (ns == 0) return 0;
-    SysDev S; S.n_orb = c->n_orb; S.n_elec = c->n_elec; S.h_core = c->d_h; S.eris = c->d_eris; S.hb = c->d_hb; S.hf_en = c->hf_en; S.spin_parity = c->spin_parity;
+    const SysDev S = fr_sysdev(c);
     if (c->full_cap < ns) full_reserve(c);
     // the determinants with a non-zero value, in storage order
     const unsigned gt = fr_blocks(ns, FR_TILE);
