@@ -1,6 +1,7 @@
 // The extern "C" boundary (include/fries_hip.h): context lifetime, the drivers' inputs, set-up and iterate entry points, the stepwise
 // operators and the estimators between two contexts.  The vector's entry points are in api_vec.hip, test hooks and statistics in api_test.hip.
 #include "api.hpp"
+#include "rdm2_plan.hpp"
 
 static thread_local std::string g_err;
 void fr_set_error(const std::string &m) { g_err = m; }
@@ -35,6 +36,8 @@ extern "C" int fries_ctx_create(fries_ctx **out, int device) {
         if (getenv("FRIES_FKS_SEQ")) h->c.fks_force_seq = atoi(getenv("FRIES_FKS_SEQ")) != 0;
         if (getenv("FRIES_FKS_NO_MERGED_NORM")) h->c.fks_no_merged_norm = atoi(getenv("FRIES_FKS_NO_MERGED_NORM")) != 0;
         if (getenv("FRIES_NO_WARM")) h->c.warm_start = false;
+        h->c.rdm2_records = R2_DEFAULT_RECORDS;      // 2^25: the fastest of 2^22 / 2^25 / 2^28 on the N2 shape at m = 1e6 (1289 / 937 / 968 ms per call)
+        if (getenv("FRIES_RDM2_RECORDS")) h->c.rdm2_records = std::min<uint64_t>(strtoull(getenv("FRIES_RDM2_RECORDS"), nullptr, 10), R2_MAX_RECORDS);
         {
             hipDeviceProp_t pr;
             FR_HIP(hipGetDeviceProperties(&pr, device));
@@ -470,5 +473,12 @@ extern "C" int fries_rdm1(fries_ctx *a, fries_ctx *b, double *gamma, fries_rdm1_
     return fr_api([&] {
         if (!a || !b || !gamma || !out) throw FriesError("fries_rdm1: null argument");
         fr_rdm1(&a->c, &b->c, gamma, out);
+    });
+}
+// the two-body density matrix between two contexts' vectors: rdm2.hip
+extern "C" int fries_rdm2(fries_ctx *a, fries_ctx *b, double *gamma2, fries_rdm2_result *out) {
+    return fr_api([&] {
+        if (!a || !b || !gamma2 || !out) throw FriesError("fries_rdm2: null argument");
+        fr_rdm2(&a->c, &b->c, gamma2, out);
     });
 }

@@ -141,6 +141,7 @@ struct FriesCtx {
     FqWork fqw{};
     // Hubbard-Holstein driver (hh.hip)
     bool hh_mode = false, hh_keep0 = false;
+    uint64_t rdm2_records = 1ull << 25;      // FRIES_RDM2_RECORDS: bin records one chunk of fries_rdm2 may hold (= R2_DEFAULT_RECORDS of rdm2_plan.hpp, where the choice is recorded)
     int spin_parity = 0;                     // fries_set_spin_parity: +-1 = time-reversal symmetrised vectors (k_enum, k_final_eval_piv)
     fries_hh_params hh{};
     uint32_t *d_vec_scr = nullptr;
@@ -345,3 +346,5 @@ uint64_t fr_h_offdiag_vec(FriesCtx *c, double h_fac);
 void fr_h_dot(FriesCtx *a, FriesCtx *b, fries_hdot_result *out);
 // rdm1.hip
 void fr_rdm1(FriesCtx *a, FriesCtx *b, double *gamma, fries_rdm1_result *out);
+// rdm2.hip
+void fr_rdm2(FriesCtx *a, FriesCtx *b, double *gamma2, fries_rdm2_result *out);

@@ -4,7 +4,7 @@
 //   frisys_mol_hip --fcidump_path F --point_group D2h --distribution HB_unnorm --vec_nonz N --mat_nonz N --max_dets N
 //                  [--target T] [--initiator I] [--epsilon E] [--max_iter K] [--result_dir DIR/] [--load_dir DIR/]
 //                  [--ini_vec PREFIX] [--trial_vec PREFIX] [--det_space FILE] [--ham_shift E] [--seed S] [--device D]
-//                  [--replicas R [--repl_every K] [--repl_rdm1 1]]
+//                  [--replicas R [--repl_every K] [--repl_rdm1 1] [--repl_rdm2 1]]
 //
 // Host side only: option parsing (argparse there, a loop here), the FCIDUMP reader (parse_fcidump / convert_symm,
 // FRIES/io_utils.cpp:189-318), the text outputs projnum.txt / projden.txt / S.txt / norm.txt / nkept.txt / params.txt
@@ -34,6 +34,11 @@
 //   * --repl_rdm1 1 (needs --replicas): at every meeting, after the fries_h_dot pairs, fries_rdm1 for the same pairs in the same order; one
 //     line per pair goes to <result_dir>replrdm1.txt: the n_orb^2 values of gamma(r, s), r < s, row-major and comma-separated (the shorter
 //     vector enumerates and the matrix is transposed back).  Every other output file is what it is without the flag.
+//   * --repl_rdm2 1 (needs --replicas): at every meeting, after the fries_h_dot and the --repl_rdm1 pairs, fries_rdm2 for the same pairs in
+//     the same order.  The n_orb^4 doubles of gamma2(r, s), row-major and little-endian, are appended to <result_dir>replrdm2.dat (binary:
+//     a line of text would be some 10 MB); one line per pair goes to <result_dir>replrdm2e.txt: the energy
+//     (sum h_pq gamma[p][q] + 1/2 sum (pq|rs) gamma2[p][q][r][s]) / <a|b> from the pair's fries_rdm1 and fries_rdm2.  Every other
+//     output file is what it is without the flag.
 #include "driver_common.hpp"
 #include <sstream>
 #include <random>
@@ -55,6 +60,7 @@ struct Args {
     std::vector<int> devices;           // --devices: GPU of every thread rank
     uint32_t replicas = 0, repl_every = 0;      // --replicas / --repl_every: independent runs inside this process and how often they are compared
     bool repl_rdm1 = false;                     // --repl_rdm1: the one-body density matrix of every pair at every meeting
+    bool repl_rdm2 = false;                     // --repl_rdm2: the two-body density matrix of every pair at every meeting
 };
 
 static Args parse_args(int argc, char **argv) {
@@ -90,6 +96,10 @@ static Args parse_args(int argc, char **argv) {
     if (kv.count("repl_rdm1")) {
         if (!r.replicas) throw std::runtime_error("--repl_rdm1 needs --replicas");
         r.repl_rdm1 = std::stoul(kv["repl_rdm1"]) != 0;
+    }
+    if (kv.count("repl_rdm2")) {
+        if (!r.replicas) throw std::runtime_error("--repl_rdm2 needs --replicas");
+        r.repl_rdm2 = std::stoul(kv["repl_rdm2"]) != 0;
     }
     if (kv.count("devices")) { std::stringstream ss(kv["devices"]); std::string t; while (std::getline(ss, t, ',')) r.devices.push_back(std::stoi(t)); }
     return r;
@@ -164,14 +174,15 @@ static bool load_last_line(const std::string &path, double *out) {
 // with an exception instead of leaving it at a barrier nobody else will reach.
 struct Replicas {
     const int R, precision;
-    const bool want_rdm1;
+    const bool want_rdm1, want_rdm2;
     uint32_t n_orb = 0;
+    const Fcidump &mol;
     std::vector<fries_ctx *> ctx;
-    std::ofstream num_file, den_file, iter_file, rdm1_file;
+    std::ofstream num_file, den_file, iter_file, rdm1_file, rdm2_file, rdm2e_file;
     std::mutex mu;
     std::condition_variable cv;
     int arrived = 0; uint64_t generation = 0; bool aborted = false;
-    Replicas(int R_, const Args &args, uint32_t n_orb_) : R(R_), precision(args.precision), want_rdm1(args.repl_rdm1), n_orb(n_orb_), ctx((size_t)R_, nullptr) {
+    Replicas(int R_, const Args &args, const Fcidump &in) : R(R_), precision(args.precision), want_rdm1(args.repl_rdm1), want_rdm2(args.repl_rdm2), n_orb(in.n_orb), mol(in), ctx((size_t)R_, nullptr) {
         const std::string &rd = args.result_dir;
         num_file.open(rd + "replnum.txt", std::ofstream::app); den_file.open(rd + "replden.txt", std::ofstream::app); iter_file.open(rd + "repliter.txt", std::ofstream::app);
         if (!num_file.is_open() || !den_file.is_open() || !iter_file.is_open()) throw std::runtime_error("Could not open file for writing in directory " + rd);
@@ -180,6 +191,12 @@ struct Replicas {
             rdm1_file.open(rd + "replrdm1.txt", std::ofstream::app);
             if (!rdm1_file.is_open()) throw std::runtime_error("Could not open file for writing in directory " + rd);
             rdm1_file.precision(precision);
+        }
+        if (want_rdm2) {
+            rdm2_file.open(rd + "replrdm2.dat", std::ofstream::app | std::ofstream::binary);
+            rdm2e_file.open(rd + "replrdm2e.txt", std::ofstream::app);
+            if (!rdm2_file.is_open() || !rdm2e_file.is_open()) throw std::runtime_error("Could not open file for writing in directory " + rd);
+            rdm2e_file.precision(precision);
         }
     }
     void abort() { std::lock_guard<std::mutex> lk(mu); aborted = true; cv.notify_all(); }
@@ -200,7 +217,10 @@ struct Replicas {
         for (int r = 0; r < R; r++) for (int s = r + 1; s < R; s++) one(r, s);
         num_file << '\n'; den_file << '\n'; iter_file << iters_done << '\n';
         num_file.flush(); den_file.flush(); iter_file.flush();
-        if (!want_rdm1) return;
+        if (want_rdm1) evaluate_rdm1(nz);
+        if (want_rdm2) evaluate_rdm2(nz);
+    }
+    void evaluate_rdm1(const std::vector<int32_t> &nz) {
         // fries_rdm1 for the same pairs in the same order: gamma(r, s), the shorter vector enumerating and the matrix transposed back
         std::vector<double> g((size_t)n_orb * n_orb);
         auto one_rdm1 = [&](int r, int s) {
@@ -217,6 +237,34 @@ struct Replicas {
         if (R == 1) one_rdm1(0, 0);
         for (int r = 0; r < R; r++) for (int s = r + 1; s < R; s++) one_rdm1(r, s);
         rdm1_file.flush();
+    }
+    void evaluate_rdm2(const std::vector<int32_t> &nz) {
+        // fries_rdm2 for the same pairs in the same order: gamma2(r, s), the shorter vector enumerating and the result transposed back
+        // ([p][q][r][s] -> [q][p][s][r]); the energy takes the pair's fries_rdm1 with it
+        const size_t n = n_orb, n2 = n * n, n4 = n2 * n2;
+        std::vector<double> g1(n2), g2(n4), out(n4);
+        auto one_rdm2 = [&](int r, int s) {
+            const bool swap = nz[r] > nz[s];
+            fries_rdm1_result res1; fries_rdm2_result res2;
+            ck(fries_rdm1(ctx[swap ? s : r], ctx[swap ? r : s], g1.data(), &res1));
+            ck(fries_rdm2(ctx[swap ? s : r], ctx[swap ? r : s], g2.data(), &res2));
+            double e1 = 0, e2 = 0;
+            for (size_t p = 0; p < n; p++)
+                for (size_t q = 0; q < n; q++) {
+                    e1 += mol.hcore[p * n + q] * g1[swap ? q * n + p : p * n + q];
+                    for (size_t r_ = 0; r_ < n; r_++)
+                        for (size_t s_ = 0; s_ < n; s_++) {
+                            const double v = swap ? g2[((q * n + p) * n + s_) * n + r_] : g2[((p * n + q) * n + r_) * n + s_];
+                            out[((p * n + q) * n + r_) * n + s_] = v;
+                            e2 += mol.eris[tri(tri(p, q), tri(r_, s_))] * v;
+                        }
+                }
+            rdm2_file.write((const char *)out.data(), (std::streamsize)(n4 * sizeof(double)));
+            rdm2e_file << (e1 + 0.5 * e2) / res2.ovlp << '\n';
+        };
+        if (R == 1) one_rdm2(0, 0);
+        for (int r = 0; r < R; r++) for (int s = r + 1; s < R; s++) one_rdm2(r, s);
+        rdm2_file.flush(); rdm2e_file.flush();
     }
     void meet(uint32_t iters_done) {
         std::unique_lock<std::mutex> lk(mu);
@@ -359,7 +407,7 @@ int main(int argc, char **argv) {
         if (args.replicas) {
             // R independent one-rank runs = R threads of this process, started like the --ranks threads below
             const int R = (int)args.replicas;
-            Replicas repl(R, args, in.n_orb);
+            Replicas repl(R, args, in);
             std::vector<std::string> errs((size_t)R);
             std::vector<std::thread> th;
             for (int r = 0; r < R; r++)

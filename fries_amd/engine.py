@@ -29,7 +29,7 @@ EXPORTS = [
     "fries_set_proc_scrambler", "fries_tie_margins", "fries_measure_copy_bandwidth", "fries_piv_stats", "fries_set_trial_vector", "fries_set_initial_vector", "fries_set_ham_shift", "fries_vec_add_to", "fries_death_clone", "fries_dots", "fries_find_preserve", "fries_sys_comp",
     "fries_vec_column_download", "fries_vec_column_upload", "fries_vec_column_zero", "fries_vec_diag_download", "fries_vec_dot_list", "fries_vec_add_vecs", "fries_set_det_space", "fries_vec_set_dense", "fries_dense_sizes", "fries_hostcomm_create", "fries_set_vec_scrambler", "fries_hh_comp_sub", "fries_hh_ref_ovlp", "fries_set_spin_parity", "fries_h_offdiag_list",
     "fries_spawn_from_comp", "fries_dense_apply", "fries_dense_norm", "fries_dense_h_count", "fries_comp_download",
-    "fries_h_dot", "fries_rdm1",
+    "fries_h_dot", "fries_rdm1", "fries_rdm2",
 ]
 
 
@@ -123,6 +123,50 @@ class Rdm1(NamedTuple):
     def transposed(self) -> "Rdm1":
         """gamma(b, a) from gamma(a, b): the matrix transposed, everything else as it is."""
         return self._replace(gamma=np.ascontiguousarray(self.gamma.T))
+
+
+class Rdm2Result(C.Structure):
+    """struct fries_rdm2_result"""
+    _fields_ = [("ovlp", C.c_double), ("abs_sum", C.c_double), ("n_src", C.c_uint64), ("n_terms", C.c_uint64), ("n_hits", C.c_uint64)]
+
+
+class Rdm2(NamedTuple):
+    """fries_rdm2's result: gamma2[p, q, r, s] = sum over sigma, tau of <a| c+_{p sigma} c+_{r tau} c_{s tau} c_{q sigma} |b> (chemists'
+    order, an [n_orb] * 4 array), ovlp = <a|b>, abs_sum = the sum of |a_i b_j| over the hits; the counts of sources, probes and probes
+    that found a non-zero value in b.  The methods are host arithmetic on the array."""
+    gamma2: np.ndarray
+    ovlp: float
+    abs_sum: float
+    n_src: int
+    n_terms: int
+    n_hits: int
+
+    def transposed(self) -> "Rdm2":
+        """gamma2(b, a) from gamma2(a, b): the adjoint, [p, q, r, s] -> [q, p, s, r]; everything else as it is."""
+        return self._replace(gamma2=np.ascontiguousarray(self.gamma2.transpose(1, 0, 3, 2)))
+
+    def partial_trace(self, n_elec: int) -> np.ndarray:
+        """sum_r gamma2[p, q, r, r] / (n_elec - 1): the one-body density matrix gamma[p, q] of fries_rdm1, up to rounding."""
+        return np.einsum("pqrr->pq", self.gamma2) / (n_elec - 1)
+
+    def expectation(self, op4) -> float:
+        """<a| O |b> / <a|b> of the two-electron operator 1/2 sum op4[p, q, r, s] c+_p c+_r c_s c_q (chemists' order, spin-summed)."""
+        op4 = np.asarray(op4, dtype=np.float64)
+        if op4.shape != self.gamma2.shape:
+            raise ValueError(f"the operator array must have shape {self.gamma2.shape}")
+        return float(0.5 * np.sum(op4 * self.gamma2) / self.ovlp)
+
+    def energy(self, h_core, eri4, gamma1) -> float:
+        """(sum(h_core * gamma1) + 1/2 sum(eri4 * gamma2)) / ovlp with eri4[p, q, r, s] = (pq|rs) and gamma1 the matrix of fries_rdm1
+        for the same pair: the total electronic energy <a|H|b> / <a|b>."""
+        h_core, eri4, gamma1 = (np.asarray(x, dtype=np.float64) for x in (h_core, eri4, gamma1))
+        if eri4.shape != self.gamma2.shape or h_core.shape != self.gamma2.shape[:2] or gamma1.shape != h_core.shape:
+            raise ValueError(f"h_core and gamma1 must have shape {self.gamma2.shape[:2]}, eri4 {self.gamma2.shape}")
+        return float((np.sum(h_core * gamma1) + 0.5 * np.sum(eri4 * self.gamma2)) / self.ovlp)
+
+    def spin_squared(self, n_elec: int) -> float:
+        """<S^2> = -N (N - 4) / 4 - 1/2 sum_pq gamma2[p, q, q, p] / ovlp"""
+        return float(-n_elec * (n_elec - 4) / 4.0 - 0.5 * np.einsum("pqqp->", self.gamma2) / self.ovlp)
 
 
 ITERLOG_DTYPE = np.dtype([("numer", "f8"), ("denom", "f8"), ("shift", "f8"), ("norm", "f8"), ("nkept", "u4"), ("n_nonz", "i4"),
@@ -226,6 +270,7 @@ def load_library() -> C.CDLL:
     lib.fries_comp_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.fries_h_dot.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(HdotResult)]
     lib.fries_rdm1.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Rdm1Result)]
+    lib.fries_rdm2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Rdm2Result)]
     _lib = lib
     return lib
 
@@ -573,6 +618,15 @@ class FriEngine:
         r = Rdm1Result()
         self._ck(self.lib.fries_rdm1(self.h, (self if other is None else other).h, _ptr(g), C.byref(r)))
         return Rdm1(g, r.ovlp, r.abs_sum, int(r.n_src), int(r.n_terms), int(r.n_hits))
+
+    def rdm2(self, other=None) -> Rdm2:
+        """The two-body density matrix between column 0 of the two engines' vectors (fries_rdm2), spin-summed, chemists' order.  self is
+        the enumerating side; other=None means the engine itself.  Neither engine may be inside another call on another thread."""
+        n = max(self.mol.n_orb if self.mol is not None else 0, 1)       # (a context without a molecule is refused by the call itself)
+        g = np.zeros((n, n, n, n))
+        r = Rdm2Result()
+        self._ck(self.lib.fries_rdm2(self.h, (self if other is None else other).h, _ptr(g), C.byref(r)))
+        return Rdm2(g, r.ovlp, r.abs_sum, int(r.n_src), int(r.n_terms), int(r.n_hits))
 
     def variational_energy(self) -> float:
         """The Rayleigh quotient <v|H|v> / <v|v> of the current vector, on the scale of numer / denom."""

@@ -4,7 +4,8 @@ A FRI run is one Markov chain; error bars, and any estimator built from two unco
 holds ``n`` engines with seeds ``seed, seed + 1, ...``; each has its own context and HIP stream, so their fused loops run side by
 side from one Python thread each (ctypes releases the GIL for the length of a call).  Replica ``r`` computes exactly what a lone
 ``FriEngine`` with seed ``seed + r`` computes.  ``pair_estimates`` evaluates ``fries_h_dot`` (the reference's calc_h_dot as
-obs_repl_mol uses it) for every pair of replicas, ``pair_rdm1`` the one-body density matrix ``fries_rdm1``.
+obs_repl_mol uses it) for every pair of replicas, ``pair_rdm1`` the one-body density matrix ``fries_rdm1``,
+``pair_rdm2`` the two-body density matrix ``fries_rdm2``.
 """
 from __future__ import annotations
 
@@ -72,6 +73,18 @@ class FriReplicas:
                 out.append(self.engines[r].rdm1(self.engines[s]))
             else:
                 out.append(self.engines[s].rdm1(self.engines[r]).transposed())
+        return out
+
+    def pair_rdm2(self):
+        """fries_rdm2 for all pairs r < s, in the order of pairs(): a list of Rdm2 whose gamma2 is always gamma2(r, s).  The replica with
+        fewer stored determinants enumerates (a tie goes to r); where that is s, the result is transposed back ([p,q,r,s] -> [q,p,s,r])."""
+        sizes = [e.vec_info()[1] for e in self.engines]
+        out = []
+        for r, s in self.pairs():
+            if sizes[r] <= sizes[s]:
+                out.append(self.engines[r].rdm2(self.engines[s]))
+            else:
+                out.append(self.engines[s].rdm2(self.engines[r]).transposed())
         return out
 
     def pairs(self):

@@ -333,10 +333,40 @@ int fries_h_dot(fries_ctx *a, fries_ctx *b, fries_hdot_result *out);
  * Refused with a message and without a launch: a null argument, a context without a molecule or without a solution vector, a
  * Hubbard-Holstein context, a context with a communicator, contexts on different devices or that differ in n_orb, n_elec or irreps, and
  * spin_parity != 0 on either side (a time-reversal vector stores one representative per pair).  hf_en plays no part and is not compared.
- * Out of scope: fries_rdm1 over ranks, time-reversal vectors, Hubbard-Holstein, two-body density matrices, the importance-weighted
+ * Out of scope: fries_rdm1 over ranks, time-reversal vectors, Hubbard-Holstein, the importance-weighted
  * compression of observables_mol (weight_vec, --exponent), a binding in include/FRIES, and replicas for drivers other than frisys_mol_hip. */
 typedef struct { double ovlp, abs_sum; uint64_t n_src, n_terms, n_hits; } fries_rdm1_result;
 int fries_rdm1(fries_ctx *a, fries_ctx *b, double *gamma /* n_orb * n_orb, row-major */, fries_rdm1_result *out);
+/* The two-body density matrix between two replicas, spin-summed and in chemists' order, over column 0 of the two contexts' solution vectors:
+ *   gamma2[((p * n_orb + q) * n_orb + r) * n_orb + s] = sum over sigma, tau of <a| c+_{p sigma} c+_{r tau} c_{s tau} c_{q sigma} |b>
+ * Bit p of a determinant is orbital p with spin alpha, bit p + n_orb orbital p with spin beta; every operator's sign is the parity of the
+ * occupied bits below it at its turn.  Three kinds of pairs (i, j) contribute a_i * sign * b_j: i == j (the diagonal: every ordered pair
+ * of occupied spin orbitals P != R gives +1 to [p][p][r][r] and, with equal spins, -1 to [p][r][r][p]), pairs one same-spin replacement
+ * apart (the replacement times every spectator, direct and same-spin exchange) and pairs two replacements apart (the two direct and the
+ * two exchange pairings, each where its spins match).  With gamma of fries_rdm1 and (pq|rs) the molecule's integrals:
+ *   sum_pq h_pq gamma[p][q] + 1/2 sum_pqrs (pq|rs) gamma2[p][q][r][s] = <a|H|b>    (fries_h_dot's h + hf_energy * ovlp)
+ *   sum_r gamma2[p][q][r][r] = (n_elec - 1) gamma[p][q];   sum_pr gamma2[p][p][r][r] = n_elec (n_elec - 1) <a|b>
+ *   gamma2[p][q][r][s] == gamma2[r][s][p][q] bit for bit;   gamma2(a, b)[p][q][r][s] = gamma2(b, a)[q][p][s][r]
+ *   <S^2> = -N (N - 4) / 4 - 1/2 sum_pq gamma2[p][q][q][p] / ovlp
+ *   ovlp    = <a|b>;  abs_sum = the sum of |a_i b_j| over the hits, once per hit
+ *   n_src   = stored determinants of `a` with a non-zero value;  n_hits = probes that found a non-zero value in b
+ *   n_terms = probes issued: per source its 2 h (n - h) singles, 2 C(h,2) C(n-h,2) same-spin and h^2 (n - h)^2 opposite-spin doubles
+ *             (h = electrons per spin, n = n_orb; counted from the determinant's own occupation)
+ * No symmetry is consulted: a bin whose four irreps do not multiply to the identity is the sum of whatever the vectors hold.
+ * As in fries_rdm1: `a` enumerates and `b` is only probed (pass the shorter vector as `a` and use the adjoint relation); neither vector,
+ * diagonal cache nor host mirror changes; a == b is allowed; the kernels run on a's stream after everything b's stream holds at the time of
+ * the call, the call returns when the result is on the host, and neither context may be inside another call on another thread meanwhile.
+ * Deterministic: no floating-point atomics; a counting pass sizes the bin records, the positions are cut into chunks of at most
+ * FRIES_RDM2_RECORDS records (read when `a` is created; default 2^25, 24 bytes each), each chunk is sorted by bin with a stable sort and
+ * added in order.  Two calls on the same vectors with the same capacity return the same bits.  Nothing stays allocated.
+ * Refused with a message and before the first launch: a null argument, a context without a molecule or without a solution vector, a
+ * Hubbard-Holstein context, a context with a communicator, contexts on different devices or that differ in n_orb, n_elec or irreps, and
+ * spin_parity != 0 on either side.  hf_en is not compared.  Refused after the counting pass, before any record is written: 32 positions
+ * whose records exceed the capacity, and scratch that exceeds the free device memory.
+ * Out of scope: ranks, time-reversal vectors, Hubbard-Holstein, three-body quantities, the importance-weighted compression of
+ * observables_mol, a binding in include/FRIES, replicas for other drivers, and skipping probes by point-group symmetry. */
+typedef struct { double ovlp, abs_sum; uint64_t n_src, n_terms, n_hits; } fries_rdm2_result;
+int fries_rdm2(fries_ctx *a, fries_ctx *b, double *gamma2 /* n_orb^4, row-major */, fries_rdm2_result *out);
 
 /* The hot-path operators one by one, on the context's solution vector. */
 /* apply_HBPP_sys (heat_bathPP.cpp:686-992) with the five uniforms it would draw; outputs as
