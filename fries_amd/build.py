@@ -58,8 +58,11 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 DRIVER = os.path.join(HERE, "frisys_mol_hip")
-REF_API_DRIVER = os.path.join(HERE, "..", "tests", "cpp", "frisys_mol_ref_api")        # a TEST consumer of include/FRIES (tests/cpp/frisys_mol_ref_api.cpp), not part of the product
-DEVICE_LOOP_DRIVER = os.path.join(HERE, "..", "tests", "cpp", "frisys_mol_device_loop")  # the same loop on include/FRIES/device_loop.hpp (tests/cpp/frisys_mol_device_loop.cpp): no bulk PCIe per iteration
+# The two test consumers link libfries_hip.so as the drivers do and are built beside it and them (rpath $ORIGIN); their sources are
+# tests/cpp/*.cpp.  Tests find them through these names.  tests/ itself holds sources and fixtures; the one product left there is the
+# LD_PRELOAD shim below, which links nothing of this build and which tests/test_gpu_refapi.py finds by its path.
+REF_API_DRIVER = os.path.join(HERE, "frisys_mol_ref_api")        # a TEST consumer of include/FRIES (tests/cpp/frisys_mol_ref_api.cpp), not part of the product
+DEVICE_LOOP_DRIVER = os.path.join(HERE, "frisys_mol_device_loop")  # the same loop on include/FRIES/device_loop.hpp (tests/cpp/frisys_mol_device_loop.cpp): no bulk PCIe per iteration
 FIXED_CLOCK = os.path.join(HERE, "..", "tests", "cpp", "libfixed_clock.so")
 DRIVERS = {name: os.path.join(HERE, name) for name in ("frisys_mol_hip", "fciqmc_mol_hip", "frisys_hh_hip", "frifull_mol_hip", "frimulti_mol_hip")}
 
@@ -79,10 +82,10 @@ def build_drivers(force: bool = False) -> str:
     inc = os.path.join(HERE, "..", "include")
     fac_hdrs = [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(inc, "FRIES")) for f in fs]
     for exe in (REF_API_DRIVER, DEVICE_LOOP_DRIVER):
-        src = exe + ".cpp"
+        src = os.path.join(HERE, "..", "tests", "cpp", os.path.basename(exe) + ".cpp")
         if force or _stale(exe, [src, LIB] + hdrs + fac_hdrs):
             cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-I" + inc, "-I" + os.path.join(inc, "FRIES", "compat"), "-o", exe, src,
-                   "-L" + HERE, "-lfries_hip", "-Wl,-rpath,$ORIGIN/../../fries_amd", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"]
+                   "-L" + HERE, "-lfries_hip", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"]
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError(f"g++ failed on {os.path.basename(src)}:\n{r.stdout}\n{r.stderr}")

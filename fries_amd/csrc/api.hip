@@ -36,7 +36,6 @@ extern "C" int fries_ctx_create(fries_ctx **out, int device) {
         if (getenv("FRIES_FKS_SEQ")) h->c.fks_force_seq = atoi(getenv("FRIES_FKS_SEQ")) != 0;
         if (getenv("FRIES_FKS_NO_MERGED_NORM")) h->c.fks_no_merged_norm = atoi(getenv("FRIES_FKS_NO_MERGED_NORM")) != 0;
         if (getenv("FRIES_NO_WARM")) h->c.warm_start = false;
-        h->c.rdm2_records = R2_DEFAULT_RECORDS;      // 2^25: the fastest of 2^22 / 2^25 / 2^28 on the N2 shape at m = 1e6 (1289 / 937 / 968 ms per call)
         if (getenv("FRIES_RDM2_RECORDS")) h->c.rdm2_records = std::min<uint64_t>(strtoull(getenv("FRIES_RDM2_RECORDS"), nullptr, 10), R2_MAX_RECORDS);
         {
             hipDeviceProp_t pr;

@@ -141,23 +141,6 @@ __device__ __forceinline__ double fr_block_excl_f64(double tsum, double *sh /* >
     return texcl;
 }
 
-// exclusive scans across the 64 lanes of a wave (storage order), no LDS, no barrier
-__device__ __forceinline__ uint32_t fr_wave_excl_u32(uint32_t x, uint32_t *total) {
-    int lane = fr_lane();
-    uint32_t v = x;
-    for (int off = 1; off < 64; off <<= 1) { uint32_t t = __shfl_up(v, off); if (lane >= off) v += t; }
-    *total = __shfl(v, 63);
-    return v - x;
-}
-__device__ __forceinline__ double fr_wave_excl_f64(double x, double *total) {
-    int lane = fr_lane();
-    double v = x;
-    for (int off = 1; off < 64; off <<= 1) { double t = __shfl_up(v, off); if (lane >= off) v += t; }
-    *total = __shfl(v, 63);
-    double e = __shfl_up(v, 1);
-    return lane ? e : 0.0;
-}
-
 // ------------------------------------------------------------------ stage dispatch
 // Per-element row: setup -> RowInfo, visit -> (sub, normalised weight) ascending.
 template <int STAGE, bool NEW_HB>

@@ -4,6 +4,7 @@
 #include "fries_dev.hpp"
 #include "comp_kernels.hpp"
 #include "fks2.hpp"
+#include "rdm2_plan.hpp"
 #include "../../include/fries_hip.h"
 #include <string>
 #include <vector>
@@ -141,7 +142,7 @@ struct FriesCtx {
     FqWork fqw{};
     // Hubbard-Holstein driver (hh.hip)
     bool hh_mode = false, hh_keep0 = false;
-    uint64_t rdm2_records = 1ull << 25;      // FRIES_RDM2_RECORDS: bin records one chunk of fries_rdm2 may hold (= R2_DEFAULT_RECORDS of rdm2_plan.hpp, where the choice is recorded)
+    uint64_t rdm2_records = R2_DEFAULT_RECORDS;     // FRIES_RDM2_RECORDS: bin records one chunk of fries_rdm2 may hold (rdm2_plan.hpp records the choice)
     int spin_parity = 0;                     // fries_set_spin_parity: +-1 = time-reversal symmetrised vectors (k_enum, k_final_eval_piv)
     fries_hh_params hh{};
     uint32_t *d_vec_scr = nullptr;

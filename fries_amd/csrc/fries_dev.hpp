@@ -212,6 +212,28 @@ __device__ __forceinline__ uint32_t fr_wave_sum_u32(uint32_t x) {
     for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
     return x;
 }
+// exclusive scans across the 64 lanes of a wave (storage order), no LDS, no barrier
+__device__ __forceinline__ uint32_t fr_wave_excl_u32(uint32_t x, uint32_t *total) {
+    int lane = fr_lane();
+    uint32_t v = x;
+    for (int off = 1; off < 64; off <<= 1) { uint32_t t = __shfl_up(v, off); if (lane >= off) v += t; }
+    *total = __shfl(v, 63);
+    return v - x;
+}
+__device__ __forceinline__ double fr_wave_excl_f64(double x, double *total) {
+    int lane = fr_lane();
+    double v = x;
+    for (int off = 1; off < 64; off <<= 1) { double t = __shfl_up(v, off); if (lane >= off) v += t; }
+    *total = __shfl(v, 63);
+    double e = __shfl_up(v, 1);
+    return lane ? e : 0.0;
+}
+// orders a wave's LDS accesses before the fence against those after it (lanes of one wave run in lock-step; LDS serves a wave's
+// accesses in order: what is left to rule out is the compiler moving them)
+__device__ __forceinline__ void fr_wave_step_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
 __device__ __forceinline__ double fr_block_sum(double x, double *sh /* >= 4 */) {
     x = fr_wave_sum(x);
     if (fr_lane() == 0) sh[threadIdx.x >> 6] = x;

@@ -13,8 +13,7 @@
 // value is left.  The association order is a function of curr_size alone, so two calls on the same vectors return the same bits.
 #include "ctx.hpp"
 #include "enum_rows.hpp"
-#include "hdot_probe.hpp"       // hd_resolve, shared with k_rdm1
-#include "pair_frame.hpp"
+#include "pair_frame.hpp"       // fr_pair_begin, hd_resolve: shared with fr_rdm1 and fr_rdm2
 
 #define HD_ILP 4
 #define HD_CHUNK 4096

@@ -1,8 +1,10 @@
-// What an estimator between the solution vectors of two contexts (fr_h_dot, fr_rdm1) begins with.  `who` is the entry point's name.
+// What the estimators between the solution vectors of two contexts share (hdot.hip: fr_h_dot / k_hdot, rdm1.hip: fr_rdm1 / k_rdm1,
+// rdm2.hip: fr_rdm2 / k_rdm2_probe): on the host how a call begins, on the device how `b` is looked up.  `who` is the entry point's name.
 #pragma once
 #include "ctx.hpp"
 #include <cstring>
 
+// ------------------------------------------------------------------ host
 // Refuses what no such estimator handles -- everything that refuses comes before the first launch --, makes a's stream wait for what
 // b's stream has enqueued so far (`b` is only read: it must have run before the probes start) and reads a's curr_size back.
 // -> n_pos, checked against the capacity; the caller adds its own refusals, zeroes its outputs and leaves at once when n_pos == 0.
@@ -31,3 +33,57 @@ static inline uint32_t fr_pair_begin(const char *who, FriesCtx *a, FriesCtx *b) 
     if (n_pos > a->vec.cap) throw FriesError(w + "the vector's size exceeds its capacity");
     return n_pos;
 }
+// ... and what the density matrices refuse on top: their kernels split a determinant into two n_orb-bit halves and walk it as it is stored
+static inline uint32_t fr_pair_begin_rdm(const char *who, FriesCtx *a, FriesCtx *b) {
+    const uint32_t n_pos = fr_pair_begin(who, a, b);
+    const std::string w = std::string(who) + ": ";
+    if (a->n_orb > FR_MAX_ORB) throw FriesError(w + "more than 32 orbitals");
+    for (const FriesCtx *c : {a, b})
+        if (c->spin_parity != 0) throw FriesError(w + "a context with spin_parity != 0 stores one representative per time-reversal pair; unfolding it is out of scope");
+    return n_pos;
+}
+// refuses, before anything is launched, a scratch array sized from n_pos that the device has no room for
+static inline void fr_need_free(const char *who, size_t bytes, const char *what, uint32_t n_pos) {
+    size_t free_b = 0, total_b = 0;
+    FR_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (bytes > free_b) {
+        std::ostringstream os;
+        os << who << ": " << what << " of " << n_pos << " positions need " << bytes << " bytes of device memory, " << free_b << " are free";
+        throw FriesError(os.str());
+    }
+}
+
+// ------------------------------------------------------------------ device
+// The look-up: the caller loads the first 16-byte slot of every candidate of a round itself, so that those loads are independent of
+// each other, and resolves them afterwards.
+// -> value of determinant d in column 0 of V; 0 for a miss.  e = the slot the first probe returned.
+__device__ __forceinline__ double hd_resolve(const VecDev &V, det_t d, uint32_t s, HSlot e) {
+    const uint32_t mask = V.hcap - 1;
+    for (uint32_t probe = 0; probe < V.hcap; probe++) {
+        if (e.key == d) return e.val < V.cap ? V.v0[e.val] : 0.0;
+        if (e.key == FR_EMPTY_KEY) return 0.0;
+        s = (s + 1) & mask;
+        e = V.hs[s];
+    }
+    return 0.0;
+}
+
+// One source of a wave of k_rdm1 / k_rdm2_probe: every lane holds one position's (value, determinant), the wave walks them in order.
+struct PairSrc {
+    double av; det_t det;       // the source, broadcast from the lane that holds it
+    uint32_t sl0; HSlot e0;     // the first probe of the source itself in B (overlap, diagonal): in flight while the candidates are formed
+    det_t occ0, occ1;           // the alpha / beta halves (n_orb <= 32)
+    unsigned no0, no1;          // ... and their electrons
+    // false: a hole, a zeroed entry or past the end (uniform over the wave); nothing else is set then
+    // lowmask = the low n_orb bits
+    __device__ __forceinline__ bool load(const VecDev &B, double my_val, unsigned long long my_det, int s, uint32_t n_orb, det_t lowmask) {
+        av = __shfl(my_val, s);
+        if (av == 0) return false;
+        det = __shfl(my_det, s);
+        sl0 = fr_hash_slot(det, B.hcap);
+        e0 = B.hs[sl0];
+        occ0 = det & lowmask; occ1 = (det >> n_orb) & lowmask;
+        no0 = __popcll(occ0); no1 = __popcll(occ1);
+        return true;
+    }
+};

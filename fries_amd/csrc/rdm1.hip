@@ -16,7 +16,6 @@
 // RD_FAN of them per workgroup in index order, level by level until one is left.  The order in which every bin's terms are associated is
 // a function of curr_size and the positions alone: two calls on the same vectors return the same bits.
 #include "ctx.hpp"
-#include "hdot_probe.hpp"
 #include "rdm1_plan.hpp"
 #include "pair_frame.hpp"
 
@@ -27,13 +26,6 @@
 #define RD_LDS_ORB FR_MAX_ORB   // edge of a wave's matrix in LDS (diagnostic builds: a larger one lowers the occupancy)
 #endif
 
-// orders the LDS read-modify-writes of one step before those of the next (lanes of one wave run in lock-step; LDS serves a wave's
-// accesses in order: what is left to rule out is the compiler moving them)
-__device__ __forceinline__ void rd_step_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // part: [gridDim.x][n_orb^2 + RD_NSCAL] (the matrix, ovlp, abs_sum); cnt: [gridDim.x][RD_NCNT] (n_src, n_terms, n_hits)
 __global__ void __launch_bounds__(FR_BLOCK) k_rdm1(VecDev A, VecDev B, uint32_t n_orb, uint32_t n_pos, double *part, unsigned long long *cnt) {
     __shared__ double G[4][RD_LDS_ORB * RD_LDS_ORB];
@@ -43,7 +35,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_rdm1(VecDev A, VecDev B, uint32_t 
     const unsigned n2 = n_orb * n_orb;
     double *g = G[w];
     for (unsigned k = lane; k < n2; k += FR_WAVE) g[k] = 0.0;
-    rd_step_fence();
+    fr_wave_step_fence();
     const size_t mine = (size_t)blockIdx.x * RD_BPOS + (size_t)w * RD_WPOS + lane;
     unsigned long long my_det = 0; double my_val = 0;
     if (mine < n_pos) { my_det = A.dets[mine]; my_val = A.v0[mine]; }
@@ -51,15 +43,12 @@ __global__ void __launch_bounds__(FR_BLOCK) k_rdm1(VecDev A, VecDev B, uint32_t 
     double ov = 0, ab = 0;
     uint32_t n_src = 0, n_terms = 0, n_hits = 0;
     for (int s = 0; s < RD_WPOS; s++) {
-        const double av = __shfl(my_val, s);
-        if (av == 0) continue;          // hole, zeroed entry or past the end (uniform over the wave)
-        const det_t det = __shfl(my_det, s);
+        PairSrc src;
+        if (!src.load(B, my_val, my_det, s, n_orb, lowmask)) continue;
         n_src++;
-        // the source itself in b, for the overlap and the diagonal: in flight together with the first round below
-        const uint32_t sl0 = fr_hash_slot(det, B.hcap);
-        const HSlot e0 = B.hs[sl0];
-        const det_t occ0 = det & lowmask, occ1 = (det >> n_orb) & lowmask;
-        const unsigned no0 = __popcll(occ0), no1 = __popcll(occ1);
+        const double av = src.av;
+        const det_t det = src.det, occ0 = src.occ0, occ1 = src.occ1;
+        const unsigned no0 = src.no0, no1 = src.no1;
         const unsigned nc0 = no0 * (n_orb - no0), nc1 = no1 * (n_orb - no1);
         const unsigned pad0 = (nc0 + FR_WAVE - 1) & ~(FR_WAVE - 1u), n_idx = pad0 + ((nc1 + FR_WAVE - 1) & ~(FR_WAVE - 1u));
         for (unsigned c0 = 0; c0 < n_idx; c0 += FR_WAVE * RD_ILP) {
@@ -93,15 +82,15 @@ __global__ void __launch_bounds__(FR_BLOCK) k_rdm1(VecDev A, VecDev B, uint32_t 
                         ab += fabs(t); n_hits++;
                     }
                 }
-                rd_step_fence();
+                fr_wave_step_fence();
             }
         }
-        const double t = av * hd_resolve(B, det, sl0, e0);
+        const double t = av * hd_resolve(B, det, src.sl0, src.e0);
         if (t != 0) {
             if (lane == 0) ov += t;
             for (int spin = 0; spin < 2; spin++) {
                 if (lane < (spin ? no1 : no0)) { const unsigned p = fr_nth_bit(spin ? occ1 : occ0, lane); g[p * n_orb + p] += t; }
-                rd_step_fence();
+                fr_wave_step_fence();
             }
         }
     }
@@ -132,10 +121,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_rdm1_reduce(const double *in_d, co
 }
 
 void fr_rdm1(FriesCtx *a, FriesCtx *b, double *gamma, fries_rdm1_result *out) {
-    const uint32_t n_pos = fr_pair_begin("fries_rdm1", a, b);
-    if (a->n_orb > FR_MAX_ORB) throw FriesError("fries_rdm1: more than 32 orbitals");
-    for (const FriesCtx *c : {a, b})
-        if (c->spin_parity != 0) throw FriesError("fries_rdm1: a context with spin_parity != 0 stores one representative per time-reversal pair; unfolding it is out of scope");
+    const uint32_t n_pos = fr_pair_begin_rdm("fries_rdm1", a, b);
     hipStream_t st = a->stream;
     const size_t n2 = (size_t)a->n_orb * a->n_orb;
     *out = fries_rdm1_result{};
@@ -143,13 +129,7 @@ void fr_rdm1(FriesCtx *a, FriesCtx *b, double *gamma, fries_rdm1_result *out) {
     if (n_pos == 0) return;
     // the levels of the fold back to back; sized from n_pos and checked against what the device has left before anything is launched
     const Rdm1Plan plan = fr_rdm1_plan(n_pos, a->n_orb);
-    size_t free_b = 0, total_b = 0;
-    FR_HIP(hipMemGetInfo(&free_b, &total_b));
-    if (plan.bytes() > free_b) {
-        std::ostringstream os;
-        os << "fries_rdm1: the partial matrices of " << n_pos << " positions need " << plan.bytes() << " bytes of device memory, " << free_b << " are free";
-        throw FriesError(os.str());
-    }
+    fr_need_free("fries_rdm1", plan.bytes(), "the partial matrices", n_pos);
     DevMem tmp;
     double *d_part = tmp.alloc<double>(plan.total_rows * plan.stride);
     unsigned long long *d_cnt = tmp.alloc<unsigned long long>(plan.total_rows * RD_NCNT);

@@ -11,23 +11,19 @@
 //   1. k_rdm2_probe<false> probes and counts, per wave, the records its hits expand to (and ovlp, abs_sum and the counters).
 //   2. The host cuts the workgroups into chunks whose records fit the capacity (rdm2_plan.hpp) and scans the waves' offsets.
 //   3. Per chunk k_rdm2_probe<true> probes again and writes (bin, value) at those offsets, in (position, candidate) order;
-//   4. a stable LSD radix sort on the bin (8-bit digits, as the merge's k_rs_* in vec.hip) carries the record's index;
+//   4. a stable LSD radix sort on the bin (8-bit digits, radix_sort.hpp, shared with the merge's k_rs_* in vec.hip) carries the record's index;
 //   5. k_r2_piece adds every bin's records in sorted order in pieces that end at multiples of R2_PIECE, k_r2_fold the pieces in order
 //      onto what the chunks before left in the bin.
 // The order in which a bin's terms are associated is a function of the positions and the capacity alone.
 #include "ctx.hpp"
-#include "hdot_probe.hpp"
 #include "rdm2_plan.hpp"
 #include "pair_frame.hpp"
+#include "radix_sort.hpp"
 
 #ifndef R2_ILP
 #define R2_ILP 4                // probes a lane has in flight per round
 #endif
 
-__device__ __forceinline__ void r2_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 __device__ __forceinline__ unsigned r2_below(det_t d, unsigned x) { return __popcll(d & ((1ull << x) - 1ull)); }
 // t -> (i < j) with t = j (j - 1) / 2 + i
 __device__ __forceinline__ void r2_tri(unsigned t, unsigned *i, unsigned *j) {
@@ -35,13 +31,6 @@ __device__ __forceinline__ void r2_tri(unsigned t, unsigned *i, unsigned *j) {
     while (k * (k - 1) / 2 > t) k--;
     while ((k + 1) * k / 2 <= t) k++;
     *j = k; *i = t - k * (k - 1) / 2;
-}
-// exclusive scan of x over the wave's lanes; *total = the wave's sum
-__device__ __forceinline__ uint32_t r2_wave_excl(uint32_t x, unsigned lane, uint32_t *total) {
-    uint32_t v = x;
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(v, off); if (lane >= (unsigned)off) v += t; }
-    *total = __shfl(v, 63);
-    return v - x;
 }
 
 struct R2Out { uint32_t *key, *pay; double *val; uint32_t n_rec; };
@@ -66,21 +55,19 @@ __global__ void __launch_bounds__(FR_BLOCK) k_rdm2_probe(VecDev A, VecDev B, uin
     unsigned long long n_terms = 0, n_rec = 0;
     uint32_t base = EMIT ? wave_off[wave] : 0u;
     for (int s = 0; s < R2_WPOS; s++) {
-        const double av = __shfl(my_val, s);
-        if (av == 0) continue;          // hole, zeroed entry or past the end (uniform over the wave)
-        const det_t det = __shfl(my_det, s);
+        PairSrc src;
+        if (!src.load(B, my_val, my_det, s, n_orb, lowmask)) continue;
         n_src++;
-        const uint32_t sl0 = fr_hash_slot(det, B.hcap);
-        const HSlot e0 = B.hs[sl0];
-        const det_t occ0 = det & lowmask, occ1 = (det >> n_orb) & lowmask;
-        const unsigned no0 = __popcll(occ0), no1 = __popcll(occ1), nh0 = n_orb - no0, nh1 = n_orb - no1, n_el = no0 + no1;
-        r2_fence();
+        const double av = src.av;
+        const det_t det = src.det, occ0 = src.occ0, occ1 = src.occ1;
+        const unsigned no0 = src.no0, no1 = src.no1, nh0 = n_orb - no0, nh1 = n_orb - no1, n_el = no0 + no1;
+        fr_wave_step_fence();
         if (lane < n_orb) {
             const bool o0 = (occ0 >> lane) & 1ull, o1 = (occ1 >> lane) & 1ull;
             L[w][o0 ? 0 : 1][r2_below(o0 ? occ0 : ~occ0 & lowmask, lane)] = (uint8_t)lane;
             L[w][o1 ? 2 : 3][r2_below(o1 ? occ1 : ~occ1 & lowmask, lane)] = (uint8_t)(lane + n_orb);
         }
-        r2_fence();
+        fr_wave_step_fence();
         const unsigned ns0 = no0 * nh0, ns1 = no1 * nh1;
         const unsigned nq0 = nh0 * (nh0 - 1) / 2, nq1 = nh1 * (nh1 - 1) / 2;
         const unsigned nd0 = no0 * (no0 - 1) / 2 * nq0, nd1 = no1 * (no1 - 1) / 2 * nq1;
@@ -135,7 +122,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_rdm2_probe(VecDev A, VecDev B, uin
                 }
                 if (__ballot(nr != 0) == 0ull) continue;        // uniform
                 uint32_t tot;
-                uint32_t o = base + r2_wave_excl(nr, lane, &tot);
+                uint32_t o = base + fr_wave_excl_u32(nr, &tot);
                 base += tot; n_rec += tot;
                 if (EMIT && nr) {
                     const unsigned p = P % n_orb, q = Q % n_orb;
@@ -155,7 +142,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_rdm2_probe(VecDev A, VecDev B, uin
             }
         }
         // the source itself in b: the overlap and the diagonal, one direct and (same spin) one exchange record per occupied pair P < R
-        const double t = av * hd_resolve(B, det, sl0, e0);
+        const double t = av * hd_resolve(B, det, src.sl0, src.e0);
         if (t != 0) {
             if (lane == 0) ov += t;
             const unsigned n_pair = n_el * (n_el - 1) / 2;
@@ -169,7 +156,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_rdm2_probe(VecDev A, VecDev B, uin
                     nr = ((P >= n_orb) == (R >= n_orb)) ? 2u : 1u;
                 }
                 uint32_t tot;
-                uint32_t o = base + r2_wave_excl(nr, lane, &tot);
+                uint32_t o = base + fr_wave_excl_u32(nr, &tot);
                 base += tot; n_rec += tot;
                 if (EMIT && nr) {
                     const unsigned p = P % n_orb, r = R % n_orb;
@@ -189,82 +176,18 @@ __global__ void __launch_bounds__(FR_BLOCK) k_rdm2_probe(VecDev A, VecDev B, uin
     }
 }
 
-// ------------------------------------------------------------------ stable LSD radix sort, 8-bit digits (the shape of vec.hip's k_rs_*; n by value)
+// ------------------------------------------------------------------ stable LSD radix sort, 8-bit digits (radix_sort.hpp; the length by value)
+static_assert(R2_TILE == RS_TILE, "fr_rdm2_scratch sizes the histograms in R2_TILE");
 __global__ void __launch_bounds__(FR_BLOCK) k_r2_hist(const uint32_t *key, uint32_t n, uint32_t *hist, int shift, uint32_t nblk) {
-    __shared__ uint32_t h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const size_t base = (size_t)blockIdx.x * R2_TILE;
-    for (int it = 0; it < R2_TILE / FR_BLOCK; it++) {
-        const size_t j = base + it * FR_BLOCK + threadIdx.x;
-        if (j < n) atomicAdd(&h[(key[j] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    hist[(size_t)threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
+    fr_rs_hist_tile(key, n, hist, shift, nblk);
 }
-// one block per digit: exclusive scan of that digit's counts over the tiles; total -> hist tail
+// one block per digit
 __global__ void __launch_bounds__(FR_BLOCK) k_r2_scan(uint32_t *hist, uint32_t nblk) {
-    __shared__ uint32_t shu[4];
-    uint32_t *row = hist + (size_t)blockIdx.x * nblk;
-    uint32_t carry = 0;
-    for (unsigned b0 = 0; b0 < nblk; b0 += FR_BLOCK) {
-        const unsigned b = b0 + threadIdx.x;
-        uint32_t x = b < nblk ? row[b] : 0, tot;
-        const uint32_t incl = fr_block_scan_u32(x, shu, &tot);
-        if (b < nblk) row[b] = carry + incl - x;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) hist[(size_t)256 * nblk + blockIdx.x] = carry;
+    fr_rs_scan_digit(hist, nblk, nblk);
 }
 __global__ void __launch_bounds__(FR_BLOCK) k_r2_scatter(const uint32_t *key, const uint32_t *pay, uint32_t *key_out, uint32_t *pay_out,
                                                          uint32_t n, const uint32_t *hist, int shift, uint32_t nblk) {
-    __shared__ uint32_t wcount[4][256];
-    __shared__ uint32_t gbase[256];
-    __shared__ uint32_t shu[4];
-    const int lane = fr_lane(), w = threadIdx.x >> 6;
-    for (int q = 0; q < 4; q++) wcount[q][threadIdx.x] = 0;
-    {   // digit bases: exclusive scan of the 256 totals + this tile's offset within the digit
-        uint32_t t = hist[(size_t)256 * nblk + threadIdx.x], tot;
-        const uint32_t incl = fr_block_scan_u32(t, shu, &tot);
-        gbase[threadIdx.x] = incl - t + hist[(size_t)threadIdx.x * nblk + blockIdx.x];
-    }
-    __syncthreads();
-    // each wave owns 256 consecutive keys, visited as 4 rounds of 64 consecutive keys
-    const size_t wbase = (size_t)blockIdx.x * R2_TILE + (size_t)w * 256;
-    uint32_t kk[4], pp[4], rk[4];
-    for (int r = 0; r < 4; r++) {
-        const size_t j = wbase + r * 64 + lane;
-        const bool ok = j < n;
-        kk[r] = ok ? key[j] : 0xFFFFFFFFu; pp[r] = ok ? pay[j] : 0;
-        const uint32_t dg = (kk[r] >> shift) & 255u;
-        unsigned long long m = __ballot(ok);
-        for (int b = 0; b < 8; b++) {
-            const unsigned long long bal = __ballot((dg >> b) & 1u);
-            m &= ((dg >> b) & 1u) ? bal : ~bal;
-        }
-        if (!ok) m = 0;
-        const uint32_t before = __popcll(m & ((1ull << lane) - 1ull));
-        const uint32_t prev = ok ? wcount[w][dg] : 0;
-        rk[r] = prev + before;
-        __builtin_amdgcn_wave_barrier();
-        if (ok && before == 0) wcount[w][dg] = prev + (uint32_t)__popcll(m);
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    {   // cross-wave exclusive prefix per digit (thread d handles digit d)
-        const uint32_t a0 = wcount[0][threadIdx.x], a1 = wcount[1][threadIdx.x], a2 = wcount[2][threadIdx.x];
-        __syncthreads();
-        wcount[0][threadIdx.x] = 0; wcount[1][threadIdx.x] = a0; wcount[2][threadIdx.x] = a0 + a1; wcount[3][threadIdx.x] = a0 + a1 + a2;
-    }
-    __syncthreads();
-    for (int r = 0; r < 4; r++) {
-        const size_t j = wbase + r * 64 + lane;
-        if (j < n) {
-            const uint32_t dg = (kk[r] >> shift) & 255u;
-            const uint32_t o = gbase[dg] + wcount[w][dg] + rk[r];
-            if (o < n) { key_out[o] = kk[r]; pay_out[o] = pp[r]; }
-        }
-    }
+    fr_rs_scatter_tile(key, pay, key_out, pay_out, n, hist, shift, nblk);
 }
 
 // ------------------------------------------------------------------ segmented in-order sum
@@ -290,10 +213,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_r2_fold(const uint32_t *key, uint3
 }
 
 void fr_rdm2(FriesCtx *a, FriesCtx *b, double *gamma2, fries_rdm2_result *out) {
-    const uint32_t n_pos = fr_pair_begin("fries_rdm2", a, b);
-    if (a->n_orb > FR_MAX_ORB) throw FriesError("fries_rdm2: more than 32 orbitals");
-    for (const FriesCtx *c : {a, b})
-        if (c->spin_parity != 0) throw FriesError("fries_rdm2: a context with spin_parity != 0 stores one representative per time-reversal pair; unfolding it is out of scope");
+    const uint32_t n_pos = fr_pair_begin_rdm("fries_rdm2", a, b);
     hipStream_t st = a->stream;
     const uint32_t n = a->n_orb;
     const size_t n2 = (size_t)n * n, n4 = n2 * n2;
@@ -302,17 +222,8 @@ void fr_rdm2(FriesCtx *a, FriesCtx *b, double *gamma2, fries_rdm2_result *out) {
     if (n_pos == 0) return;
     const uint32_t n_wg = fr_blocks(n_pos, R2_BPOS);
     const size_t n_waves = (size_t)n_wg * R2_WAVES;
-    auto need_free = [&](size_t bytes, const char *what) {
-        size_t free_b = 0, total_b = 0;
-        FR_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (bytes > free_b) {
-            std::ostringstream os;
-            os << "fries_rdm2: " << what << " of " << n_pos << " positions need " << bytes << " bytes of device memory, " << free_b << " are free";
-            throw FriesError(os.str());
-        }
-    };
     // the counting pass: its arrays and the matrix are sized from n_pos and n_orb and checked before anything is launched
-    need_free(n_waves * (R2_NCNT + R2_NSCAL + 1) * 8 + n4 * 8, "the matrix and the counters");
+    fr_need_free("fries_rdm2", n_waves * (R2_NCNT + R2_NSCAL + 1) * 8 + n4 * 8, "the matrix and the counters", n_pos);
     DevMem tmp;
     unsigned long long *d_cnt = tmp.alloc<unsigned long long>(n_waves * R2_NCNT);
     double *d_scal = tmp.alloc<double>(n_waves * R2_NSCAL);
@@ -344,7 +255,7 @@ void fr_rdm2(FriesCtx *a, FriesCtx *b, double *gamma2, fries_rdm2_result *out) {
     if (a->dbg >= 1)
         fprintf(stderr, "[fries] fries_rdm2: %llu bin records in %zu chunks of at most %llu (capacity %llu), scratch %zu bytes\n", (unsigned long long)plan.total_rec,
                 plan.chunks.size(), (unsigned long long)plan.max_rec, (unsigned long long)cap, sc.bytes);
-    need_free(sc.bytes, "the bin records");
+    fr_need_free("fries_rdm2", sc.bytes, "the bin records", n_pos);
     uint8_t *d_sc = tmp.alloc<uint8_t>(sc.bytes);
     FR_HIP(hipMemsetAsync(d_G, 0, n4 * 8, st));
     FR_HIP(hipMemcpyAsync(d_off, plan.wave_off.data(), n_waves * 4, hipMemcpyHostToDevice, st));

@@ -9,6 +9,7 @@
 // atomicMin on the new hash slot plus a prefix sum, and accumulation runs over a stable
 // radix sort of (position, pass) keys so each position sums its contributions sequentially.
 #include "ctx.hpp"
+#include "radix_sort.hpp"
 #include <chrono>
 #include <cstring>
 
@@ -300,93 +301,28 @@ __global__ void __launch_bounds__(FR_BLOCK) k_spawn_resolve(VecDev V, SpawnBuf S
     key[j] = k; pay[j] = j;
 }
 
-// ------------------------------------------------------------------ stable LSD radix sort, 8-bit digits
+// ------------------------------------------------------------------ stable LSD radix sort, 8-bit digits (radix_sort.hpp; the length on the device)
+static_assert(FR_TILE == RS_TILE, "the merge's grids are cut in FR_TILE");
 __global__ void __launch_bounds__(FR_BLOCK) k_rs_hist(const uint32_t *key, const uint32_t *n_ptr, uint32_t *hist, int shift, uint32_t nblk_alloc) {
-    __shared__ uint32_t h[256];
     const uint32_t n = *n_ptr;
     const unsigned nblk = (n + FR_TILE - 1) / FR_TILE;
     if (blockIdx.x >= nblk) return;
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    size_t base = (size_t)blockIdx.x * FR_TILE;
-    for (int it = 0; it < FR_ITEMS; it++) {
-        size_t j = base + it * FR_BLOCK + threadIdx.x;
-        if (j < n) atomicAdd(&h[(key[j] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    hist[(size_t)threadIdx.x * nblk_alloc + blockIdx.x] = h[threadIdx.x];
+    fr_rs_hist_tile(key, n, hist, shift, nblk_alloc);
 }
 
-// one block per digit: exclusive scan of that digit's counts over the tiles; total -> hist tail
+// one block per digit
 __global__ void __launch_bounds__(FR_BLOCK) k_rs_scan(const uint32_t *n_ptr, uint32_t *hist, uint32_t nblk_alloc) {
-    __shared__ uint32_t shu[4];
     const uint32_t n = *n_ptr;
     const unsigned nblk = (n + FR_TILE - 1) / FR_TILE;
-    uint32_t *row = hist + (size_t)blockIdx.x * nblk_alloc;
-    uint32_t carry = 0;
-    for (unsigned b0 = 0; b0 < nblk; b0 += FR_BLOCK) {
-        unsigned b = b0 + threadIdx.x;
-        uint32_t x = b < nblk ? row[b] : 0, tot;
-        uint32_t incl = fr_block_scan_u32(x, shu, &tot);
-        if (b < nblk) row[b] = carry + incl - x;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) hist[(size_t)256 * nblk_alloc + blockIdx.x] = carry;
+    fr_rs_scan_digit(hist, nblk, nblk_alloc);
 }
 
 __global__ void __launch_bounds__(FR_BLOCK) k_rs_scatter(const uint32_t *key, const uint32_t *pay, uint32_t *key_out, uint32_t *pay_out,
                                                          const uint32_t *n_ptr, const uint32_t *hist, int shift, uint32_t nblk_alloc) {
-    __shared__ uint32_t wcount[4][256];
-    __shared__ uint32_t gbase[256];
-    __shared__ uint32_t shu[4];
     const uint32_t n = *n_ptr;
     const unsigned nblk = (n + FR_TILE - 1) / FR_TILE;
     if (blockIdx.x >= nblk) return;
-    const int lane = fr_lane(), w = threadIdx.x >> 6;
-    for (int q = 0; q < 4; q++) wcount[q][threadIdx.x] = 0;
-    {   // digit bases: exclusive scan of the 256 totals + this tile's offset within the digit
-        uint32_t t = hist[(size_t)256 * nblk_alloc + threadIdx.x], tot;
-        uint32_t incl = fr_block_scan_u32(t, shu, &tot);
-        gbase[threadIdx.x] = incl - t + hist[(size_t)threadIdx.x * nblk_alloc + blockIdx.x];
-    }
-    __syncthreads();
-    // each wave owns 256 consecutive keys, visited as 4 rounds of 64 consecutive keys
-    size_t wbase = (size_t)blockIdx.x * FR_TILE + (size_t)w * 256;
-    uint32_t kk[4], pp[4], rk[4];
-    for (int r = 0; r < 4; r++) {
-        size_t j = wbase + r * 64 + lane;
-        bool ok = j < n;
-        kk[r] = ok ? key[j] : 0xFFFFFFFFu; pp[r] = ok ? pay[j] : 0;
-        uint32_t dg = (kk[r] >> shift) & 255u;
-        unsigned long long m = __ballot(ok);
-        for (int b = 0; b < 8; b++) {
-            unsigned long long bal = __ballot((dg >> b) & 1u);
-            m &= ((dg >> b) & 1u) ? bal : ~bal;
-        }
-        if (!ok) m = 0;
-        uint32_t before = __popcll(m & ((1ull << lane) - 1ull));
-        uint32_t prev = ok ? wcount[w][dg] : 0;
-        rk[r] = prev + before;
-        __builtin_amdgcn_wave_barrier();
-        if (ok && before == 0) wcount[w][dg] = prev + (uint32_t)__popcll(m);
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    // cross-wave exclusive prefix per digit (thread d handles digit d)
-    {
-        uint32_t a0 = wcount[0][threadIdx.x], a1 = wcount[1][threadIdx.x], a2 = wcount[2][threadIdx.x];
-        __syncthreads();
-        wcount[0][threadIdx.x] = 0; wcount[1][threadIdx.x] = a0; wcount[2][threadIdx.x] = a0 + a1; wcount[3][threadIdx.x] = a0 + a1 + a2;
-    }
-    __syncthreads();
-    for (int r = 0; r < 4; r++) {
-        size_t j = wbase + r * 64 + lane;
-        if (j < n) {
-            uint32_t dg = (kk[r] >> shift) & 255u;
-            uint32_t o = gbase[dg] + wcount[w][dg] + rk[r];
-            key_out[o] = kk[r]; pay_out[o] = pp[r];
-        }
-    }
+    fr_rs_scatter_tile(key, pay, key_out, pay_out, n, hist, shift, nblk_alloc);
 }
 
 // M6: each position sums its contributions sequentially in (pass, arrival) order.

@@ -200,31 +200,33 @@ struct Replicas {
         }
     }
     void abort() { std::lock_guard<std::mutex> lk(mu); aborted = true; cv.notify_all(); }
-    // fries_h_dot for every pair, the shorter vector enumerating (the estimate is symmetric up to rounding)
+    // the pairs of a meeting in the order of the files' columns and lines: (0, 0) when there is one replica, every r < s otherwise.
+    // swap: s holds fewer determinants than r and enumerates; the caller turns the result back to (r, s)
+    template <class F> void for_pairs(const std::vector<int32_t> &nz, F fn) {
+        if (R == 1) fn(0, 0, false);
+        for (int r = 0; r < R; r++) for (int s = r + 1; s < R; s++) fn(r, s, nz[r] > nz[s]);
+    }
+    // fries_h_dot for every pair (the estimate is symmetric up to rounding)
     void evaluate(uint32_t iters_done) {
         std::vector<int32_t> nz((size_t)R, 0);
         for (int r = 0; r < R; r++) { uint32_t n, nf; ck(fries_vec_info(ctx[r], &n, &nz[r], &nf)); }
         bool first = true;
-        auto one = [&](int r, int s) {
-            const int a = nz[r] <= nz[s] ? r : s, b = a == r ? s : r;
+        for_pairs(nz, [&](int r, int s, bool swap) {
             fries_hdot_result res;
-            ck(fries_h_dot(ctx[a], ctx[b], &res));
+            ck(fries_h_dot(ctx[swap ? s : r], ctx[swap ? r : s], &res));
             if (!first) { num_file << ','; den_file << ','; }
             first = false;
             num_file << res.h; den_file << res.ovlp;
-        };
-        if (R == 1) one(0, 0);
-        for (int r = 0; r < R; r++) for (int s = r + 1; s < R; s++) one(r, s);
+        });
         num_file << '\n'; den_file << '\n'; iter_file << iters_done << '\n';
         num_file.flush(); den_file.flush(); iter_file.flush();
         if (want_rdm1) evaluate_rdm1(nz);
         if (want_rdm2) evaluate_rdm2(nz);
     }
     void evaluate_rdm1(const std::vector<int32_t> &nz) {
-        // fries_rdm1 for the same pairs in the same order: gamma(r, s), the shorter vector enumerating and the matrix transposed back
+        // fries_rdm1 for the same pairs: gamma(r, s), the matrix transposed back
         std::vector<double> g((size_t)n_orb * n_orb);
-        auto one_rdm1 = [&](int r, int s) {
-            const bool swap = nz[r] > nz[s];
+        for_pairs(nz, [&](int r, int s, bool swap) {
             fries_rdm1_result res;
             ck(fries_rdm1(ctx[swap ? s : r], ctx[swap ? r : s], g.data(), &res));
             for (uint32_t p = 0; p < n_orb; p++)
@@ -233,18 +235,15 @@ struct Replicas {
                     rdm1_file << (swap ? g[(size_t)q * n_orb + p] : g[(size_t)p * n_orb + q]);
                 }
             rdm1_file << '\n';
-        };
-        if (R == 1) one_rdm1(0, 0);
-        for (int r = 0; r < R; r++) for (int s = r + 1; s < R; s++) one_rdm1(r, s);
+        });
         rdm1_file.flush();
     }
     void evaluate_rdm2(const std::vector<int32_t> &nz) {
-        // fries_rdm2 for the same pairs in the same order: gamma2(r, s), the shorter vector enumerating and the result transposed back
+        // fries_rdm2 for the same pairs: gamma2(r, s), the result transposed back
         // ([p][q][r][s] -> [q][p][s][r]); the energy takes the pair's fries_rdm1 with it
         const size_t n = n_orb, n2 = n * n, n4 = n2 * n2;
         std::vector<double> g1(n2), g2(n4), out(n4);
-        auto one_rdm2 = [&](int r, int s) {
-            const bool swap = nz[r] > nz[s];
+        for_pairs(nz, [&](int r, int s, bool swap) {
             fries_rdm1_result res1; fries_rdm2_result res2;
             ck(fries_rdm1(ctx[swap ? s : r], ctx[swap ? r : s], g1.data(), &res1));
             ck(fries_rdm2(ctx[swap ? s : r], ctx[swap ? r : s], g2.data(), &res2));
@@ -261,9 +260,7 @@ struct Replicas {
                 }
             rdm2_file.write((const char *)out.data(), (std::streamsize)(n4 * sizeof(double)));
             rdm2e_file << (e1 + 0.5 * e2) / res2.ovlp << '\n';
-        };
-        if (R == 1) one_rdm2(0, 0);
-        for (int r = 0; r < R; r++) for (int s = r + 1; s < R; s++) one_rdm2(r, s);
+        });
         rdm2_file.flush(); rdm2e_file.flush();
     }
     void meet(uint32_t iters_done) {

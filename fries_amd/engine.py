@@ -94,8 +94,11 @@ class HDot(NamedTuple):
 
 
 class Rdm1Result(C.Structure):
-    """struct fries_rdm1_result"""
+    """struct fries_rdm1_result and, with the same fields, struct fries_rdm2_result"""
     _fields_ = [("ovlp", C.c_double), ("abs_sum", C.c_double), ("n_src", C.c_uint64), ("n_terms", C.c_uint64), ("n_hits", C.c_uint64)]
+
+
+Rdm2Result = Rdm1Result
 
 
 class Rdm1(NamedTuple):
@@ -123,11 +126,6 @@ class Rdm1(NamedTuple):
     def transposed(self) -> "Rdm1":
         """gamma(b, a) from gamma(a, b): the matrix transposed, everything else as it is."""
         return self._replace(gamma=np.ascontiguousarray(self.gamma.T))
-
-
-class Rdm2Result(C.Structure):
-    """struct fries_rdm2_result"""
-    _fields_ = [("ovlp", C.c_double), ("abs_sum", C.c_double), ("n_src", C.c_uint64), ("n_terms", C.c_uint64), ("n_hits", C.c_uint64)]
 
 
 class Rdm2(NamedTuple):

@@ -53,39 +53,33 @@ class FriReplicas:
                 raise ex
         return logs
 
-    def pair_estimates(self):
-        """fries_h_dot for all pairs r < s, in the order of pairs(): a list of HDot.  The replica with fewer stored determinants
-        is the enumerating side (H is symmetric, so the estimate is the same up to rounding; a tie goes to r)."""
+    def _pairwise(self, call, back=None):
+        """call(a, b) for all pairs r < s, in the order of pairs().  The replica with fewer stored determinants is a, the enumerating
+        side (a tie goes to r); where that is s, back(result) turns the result into that of (r, s)."""
         sizes = [e.vec_info()[1] for e in self.engines]
         out = []
         for r, s in self.pairs():
-            a, b = (r, s) if sizes[r] <= sizes[s] else (s, r)
-            out.append(self.engines[a].h_dot(self.engines[b]))
+            if sizes[r] <= sizes[s]:
+                out.append(call(self.engines[r], self.engines[s]))
+            else:
+                res = call(self.engines[s], self.engines[r])
+                out.append(back(res) if back else res)
         return out
+
+    def pair_estimates(self):
+        """fries_h_dot for all pairs r < s, in the order of pairs(): a list of HDot.  The replica with fewer stored determinants
+        is the enumerating side (H is symmetric, so the estimate is the same up to rounding; a tie goes to r)."""
+        return self._pairwise(lambda a, b: a.h_dot(b))
 
     def pair_rdm1(self):
         """fries_rdm1 for all pairs r < s, in the order of pairs(): a list of Rdm1 whose gamma is always gamma(r, s).  The replica with
         fewer stored determinants enumerates (a tie goes to r); where that is s, the matrix is transposed back."""
-        sizes = [e.vec_info()[1] for e in self.engines]
-        out = []
-        for r, s in self.pairs():
-            if sizes[r] <= sizes[s]:
-                out.append(self.engines[r].rdm1(self.engines[s]))
-            else:
-                out.append(self.engines[s].rdm1(self.engines[r]).transposed())
-        return out
+        return self._pairwise(lambda a, b: a.rdm1(b), lambda x: x.transposed())
 
     def pair_rdm2(self):
         """fries_rdm2 for all pairs r < s, in the order of pairs(): a list of Rdm2 whose gamma2 is always gamma2(r, s).  The replica with
         fewer stored determinants enumerates (a tie goes to r); where that is s, the result is transposed back ([p,q,r,s] -> [q,p,s,r])."""
-        sizes = [e.vec_info()[1] for e in self.engines]
-        out = []
-        for r, s in self.pairs():
-            if sizes[r] <= sizes[s]:
-                out.append(self.engines[r].rdm2(self.engines[s]))
-            else:
-                out.append(self.engines[s].rdm2(self.engines[r]).transposed())
-        return out
+        return self._pairwise(lambda a, b: a.rdm2(b), lambda x: x.transposed())
 
     def pairs(self):
         """(0,1), (0,2), ..., (1,2), ...: the pairs pair_estimates() reports, in its order."""

@@ -3,7 +3,7 @@
 From the bench's state at vec_nonz = mat_nonz = target = m, in one process: FriEngine.iterate_stepwise (one iteration = the single-operator
 calls of include/fries_hip.h, driven from Python) against the fused FriEngine.iterate, in alternating blocks of at least 0.5 s each that end
 in a synchronisation, after a warm-up; median and spread over the blocks.  Then where the stepwise iteration's time goes: wall time per
-call, and the kernels' own time from fries_prof_enable.  Last, tests/cpp/frisys_mol_device_loop (the C++ loop on include/FRIES/device_loop.hpp)
+call, and the kernels' own time from fries_prof_enable.  Last, frisys_mol_device_loop (tests/cpp/frisys_mol_device_loop.cpp, the C++ loop on include/FRIES/device_loop.hpp)
 restarted from the same state: time per iteration by the difference of two run lengths, PCIe bytes per iteration from FRIES_FACADE_STATS=1.
 
 usage: python tests/scripts/gpu_stepwise_cost.py [m] [blocks]
@@ -141,7 +141,7 @@ def main():
     a, b = (min((run(n) for _ in range(3)), key=lambda r: r[0]) for n in (30, 95))
     d_it = b[3] - a[3]
     per_it = (b[0] - a[0]) / d_it
-    print(f"tests/cpp/frisys_mol_device_loop (the reference's loop shape on include/FRIES/device_loop.hpp), m = {m}:")
+    print(f"frisys_mol_device_loop (tests/cpp/frisys_mol_device_loop.cpp: the reference's loop shape on include/FRIES/device_loop.hpp), m = {m}:")
     print(f"  runs of {a[3]} and {b[3]} iterations: {a[0]:.2f} s and {b[0]:.2f} s  ->  {per_it * 1e3:.2f} ms per iteration = {1.0 / per_it:.1f} iterations/s (set-up excluded by the difference)")
     print(f"  PCIe per iteration: {(b[1] - a[1]) / d_it:.0f} bytes host->device, {(b[2] - a[2]) / d_it:.0f} bytes device->host (the closing save() excluded)")
 

@@ -13,24 +13,17 @@ import numpy as np
 import pytest
 
 import golden_io
+import pair_common as pc
 from fries_amd import fcidump
+from pair_common import SMALL, U, as_map as _as_map, ne_run as _ne_run
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -53
-SMALL = dict(epsilon=0.01, vec_nonz=100, mat_nonz=100, max_dets=1000, seed=1, distribution="HB_unnorm")
 
 
 @pytest.fixture(scope="module")
 def Engine():
     from fries_amd.engine import FriEngine
     return FriEngine
-
-
-def _ne_run():
-    r = golden_io.manifest()["runs"]["ne_m2000_unnorm"]
-    return dict(epsilon=r["epsilon"], vec_nonz=r["vec_nonz"], mat_nonz=r["mat_nonz"], max_dets=r["max_dets"], target_norm=r["target_norm"],
-                initiator=r["initiator"], seed=r["seed"], distribution=r["distribution"])
 
 
 # ------------------------------------------------------------------ the host reference
@@ -43,10 +36,6 @@ def _dense(eng, dets):
         cols[int(d)] = {int(t): float(x) for t, x in zip(od, ov) if x != 0.0 and int(t) != int(d)}
     dg = eng.matrel(0, dets)[0] - eng.hf_energy
     return cols, {int(d): float(x) for d, x in zip(dets, dg)}
-
-
-def _as_map(dets, vals):
-    return {int(d): float(v) for d, v in zip(dets, vals) if v != 0.0}
 
 
 def _reference(a, b, cols, diag):
@@ -99,17 +88,9 @@ def _check_all(ea, eb, a, b, cols, diag):
 def test_whole_space_min4(Engine, mols):
     """2 electrons in 4 orbitals, C1: all 16 determinants in both vectors, in different orders, two exact zeros each."""
     mol = mols("MIN4")
-    dets = np.array([(1 << p) | (1 << (mol.n_orb + q)) for p in range(4) for q in range(4)], dtype=np.uint64)
-    rng = np.random.RandomState(20251)
-    ea, eb, eh = Engine(mol), Engine(mol), Engine(mol)
-    for e in (ea, eb, eh):
-        e.setup(epsilon=0.01, vec_nonz=50, mat_nonz=50, max_dets=1000, seed=3, distribution="HB_unnorm")
-    da, db = dets[rng.permutation(16)], dets[rng.permutation(16)]
-    va, vb = rng.standard_normal(16), rng.standard_normal(16)
-    va[[3, 11]] = 0.0
-    vb[[0, 7]] = 0.0
-    ea.vec_load(da, va)
-    eb.vec_load(db, vb)
+    ea, eb, dets, (da, va), (db, vb) = pc.min4_pair(Engine, mol, 20251)
+    eh = Engine(mol)
+    eh.setup(epsilon=0.01, vec_nonz=50, mat_nonz=50, max_dets=1000, seed=3, distribution="HB_unnorm")
     cols, diag = _dense(eh, dets)
     assert sum(len(c) for c in cols.values()) > 100         # (one irrep: nearly every pair of determinants is connected)
     res = _check_all(ea, eb, _as_map(da, va), _as_map(db, vb), cols, diag)
@@ -123,13 +104,9 @@ def test_sparse_vectors_with_symmetry_misses_and_holes(Engine, mols):
     """Two Ne runs (seeds 1 and 2), 25 iterations at vec_nonz = mat_nonz = 150: compressed vectors with released positions and a hash
     table that has seen deletions; D2h, so most candidate slots are rejected by symmetry and most targets are not in the other vector."""
     mol = mols("Ne")
-    par = dict(epsilon=0.01, vec_nonz=150, mat_nonz=150, max_dets=4000, target_norm=100.0, distribution="HB_unnorm")
-    ea, eb, eh = Engine(mol), Engine(mol), Engine(mol)
-    ea.setup(seed=1, **par)
-    eb.setup(seed=2, **par)
+    ea, eb = pc.ne_pair(Engine, mol)
+    eh = Engine(mol)
     eh.setup(**SMALL)
-    ea.iterate(25)
-    eb.iterate(25)
     (da, va), (db, vb) = ea.vector(), eb.vector()
     a, b = _as_map(da, va), _as_map(db, vb)
     assert len(a) < da.size or len(b) < db.size or ea.vec_info()[2] + eb.vec_info()[2] > 0, "no released position in either vector"
@@ -181,46 +158,26 @@ def test_time_reversal(Engine, mols, spin_parity):
 
 
 # ------------------------------------------------------------------ 4. refusals
+def _h_dot(a, b):
+    return a.h_dot(b)
+
+
 def _refused(a, b, match):
-    na, nb = a.kernel_launches, b.kernel_launches
-    with pytest.raises(RuntimeError, match=match):
-        a.h_dot(b)
-    assert (a.kernel_launches, b.kernel_launches) == (na, nb)
+    pc.refused(_h_dot, "fries_h_dot", a, b, match)
 
 
 def test_refusals_launch_nothing(Engine, mols):
-    from fries_amd.comm import LocalGroup
+    from fries_amd.engine import HdotResult
     mol = mols("Ne")
     plain = Engine(mol)
     plain.setup(**SMALL)
-    # a communicator, even of one rank
-    grp = LocalGroup(1, SMALL["mat_nonz"])
-    ranked = Engine(mol, comm=grp.comm(0, 0))
-    ranked.setup(**SMALL)
-    _refused(plain, ranked, "communicator")
-    _refused(ranked, plain, "communicator")
-    _refused(ranked, ranked, "communicator")
-    ranked.close()
-    grp.destroy()
-    # Hubbard-Holstein
-    r = golden_io.manifest()["hh_runs"]["hh_l6_m2000"]
-    hh = Engine(None)
-    hh.setup_hh(n_elec=r["n_elec"], n_sites=r["n_sites"], eps=r["eps"], U=r["U"], omega=r["omega"], g=r["g"], gs_energy=r["gs_energy"],
-                vec_nonz=100, max_dets=1000, target_norm=r["target_norm"], initiator=r["initiator"], seed=r["seed"])
-    _refused(hh, hh, "Hubbard-Holstein")
-    _refused(plain, hh, "Hubbard-Holstein")
-    hh.close()
-    # no solution vector yet
-    bare = Engine(mol)
-    _refused(plain, bare, "solution vector")
-    bare.close()
-    # different molecules: another shape, and the same shape with other integrals
-    for other_mol in (mols("H2O"), fcidump.synthetic("Ne", seed=777)):
-        other = Engine(other_mol)
-        other.setup(**SMALL)
-        _refused(plain, other, "different molecules")
-        _refused(other, plain, "different molecules")
-        other.close()
+    pc.check_common_refusals(Engine, mols, plain, _h_dot, "fries_h_dot", HdotResult)
+    # the same shape with other integrals: hf_en, the offset of the diagonal, differs
+    other = Engine(fcidump.synthetic("Ne", seed=777))
+    other.setup(**SMALL)
+    _refused(plain, other, "different molecules")
+    _refused(other, plain, "different molecules")
+    other.close()
     # different spin parity
     flipped = Engine(mol)
     flipped.setup(**SMALL)
@@ -245,32 +202,13 @@ def test_estimator_does_not_disturb_the_run(Engine, mols):
         lp.append(probed.iterate(1))
         s, o = probed.h_dot(), probed.h_dot(quiet)
         assert s == o and s.n_hits > 0          # the two engines hold the same vector
-    lq, lp = np.concatenate(lq), np.concatenate(lp)
-    assert lq.tobytes() == lp.tobytes()
-    (dq, vq), (dp, vp) = quiet.vector(), probed.vector()
-    assert vq.tobytes() == vp.tobytes() and dq.tobytes() == dp.tobytes()
+    pc.assert_same_run(quiet, probed, np.concatenate(lq), np.concatenate(lp))
     quiet.close()
     probed.close()
 
 
 def test_estimator_returns_its_device_memory(Engine, mols):
-    """fries_h_dot's partials come from a stack DevMem: added to the create / set up / iterate / close cycle of tests/test_gpu_memory.py,
-    that test's bound keeps holding."""
-    import test_gpu_memory as tm
-
-    def cycle(kind, mol):
-        a, b = Engine(mol), Engine(mol)
-        a.setup(seed=1, **tm.NE)
-        b.setup(seed=2, **tm.NE)
-        a.iterate(3)
-        b.iterate(3)
-        assert a.h_dot(b).n_src > 0 and b.h_dot().n_src > 0
-        a.close()
-        b.close()
-
-    lost = tm.lost_bytes("frisys", mols("Ne"), cycle)
-    print(f"{lost} bytes of free device memory lost over {tm.N_CYCLES} cycles with fries_h_dot; bound {tm.TOLERANCE['frisys']}")
-    assert lost <= tm.TOLERANCE["frisys"]
+    pc.check_device_memory_returned(Engine, mols("Ne"), _h_dot, "fries_h_dot")
 
 
 # ------------------------------------------------------------------ 6. FriReplicas
@@ -304,29 +242,6 @@ def test_replicas_equal_lone_engines(Engine, mols):
 
 
 # ------------------------------------------------------------------ 7. the command line
-def _cmd(exe, fc, mol, par, n_it, out, seed):
-    return [exe, "--fcidump_path", fc, "--point_group", mol.point_group, "--distribution", par["distribution"], "--vec_nonz", str(par["vec_nonz"]),
-            "--mat_nonz", str(par["mat_nonz"]), "--max_dets", str(par["max_dets"]), "--target", repr(par["target_norm"]), "--initiator", repr(par["initiator"]),
-            "--epsilon", repr(par["epsilon"]), "--max_iter", str(n_it), "--result_dir", out, "--seed", str(seed), "--precision", "17"]
-
-
-def _saved_vector(out, mol):
-    nb = (2 * mol.n_orb + 7) // 8
-    raw = np.fromfile(out + "dets0.dat", dtype=np.uint8)
-    n_saved = raw.size // nb
-    vals = np.fromfile(out + "vals0.dat", dtype=np.float64)
-    dets = np.zeros(n_saved, dtype=np.uint64)
-    for b in range(nb):
-        dets |= raw.reshape(n_saved, nb)[:, b].astype(np.uint64) << np.uint64(8 * b)
-    vals = vals[:n_saved]
-    return dets[vals != 0], vals[vals != 0]
-
-
-def _run(cmd):
-    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0 and "Exception" not in res.stderr, res.stderr[-3000:]
-
-
 def _lines(path):
     with open(path) as f:
         return f.read().split()
@@ -343,7 +258,7 @@ def test_a_failing_replica_releases_the_others(mols, tmp_path):
     os.makedirs(out)
     with open(out + "replica1", "w") as f:
         f.write("in the way\n")
-    res = subprocess.run(_cmd(build.DRIVER, fc, mol, _ne_run(), 10, out, 5) + ["--replicas", "2", "--repl_every", "5"], capture_output=True, text=True, timeout=300)
+    res = subprocess.run(pc.cmd(build.DRIVER, fc, mol, _ne_run(), 10, out, 5) + ["--replicas", "2", "--repl_every", "5"], capture_output=True, text=True, timeout=300)
     assert res.returncode != 0
     assert "Exception on replica 1" in res.stderr and "Could not" in res.stderr, res.stderr[-2000:]
     assert "Exception on replica 0 : another replica failed" in res.stderr, res.stderr[-2000:]
@@ -360,9 +275,9 @@ def test_command_line_replicas(Engine, mols, tmp_path):
     dirs = {k: str(tmp_path / k) + "/" for k in ("repl", "plain0", "plain1", "one")}
     for d in dirs.values():
         os.makedirs(d)
-    _run(_cmd(build.DRIVER, fc, mol, par, 30, dirs["repl"], seed) + ["--replicas", "2", "--repl_every", "10"])
-    _run(_cmd(build.DRIVER, fc, mol, par, 30, dirs["plain0"], seed))
-    _run(_cmd(build.DRIVER, fc, mol, par, 30, dirs["plain1"], seed + 1))
+    pc.run(pc.cmd(build.DRIVER, fc, mol, par, 30, dirs["repl"], seed) + ["--replicas", "2", "--repl_every", "10"])
+    pc.run(pc.cmd(build.DRIVER, fc, mol, par, 30, dirs["plain0"], seed))
+    pc.run(pc.cmd(build.DRIVER, fc, mol, par, 30, dirs["plain1"], seed + 1))
     for r in range(2):
         rd, pd = dirs["repl"] + f"replica{r}/", dirs[f"plain{r}"]
         names = sorted(os.listdir(pd))
@@ -378,7 +293,7 @@ def test_command_line_replicas(Engine, mols, tmp_path):
     for r in range(2):
         e = Engine(mol)
         e.setup(**dict(par, seed=seed + r))
-        e.vec_load(*_saved_vector(dirs["repl"] + f"replica{r}/", mol))
+        e.vec_load(*pc.saved_vector(dirs["repl"] + f"replica{r}/", mol))
         engs.append(e)
     a, b = (0, 1) if engs[0].vec_info()[1] <= engs[1].vec_info()[1] else (1, 0)
     res = engs[a].h_dot(engs[b])
@@ -387,7 +302,7 @@ def test_command_line_replicas(Engine, mols, tmp_path):
     assert abs(float(num[-1]) - res.h) <= bound
     assert abs(float(den[-1]) - res.ovlp) <= bound
     # one replica: the pair (0, 0), the Rayleigh quotient of the vector
-    _run(_cmd(build.DRIVER, fc, mol, par, 30, dirs["one"], seed) + ["--replicas", "1", "--repl_every", "10"])
+    pc.run(pc.cmd(build.DRIVER, fc, mol, par, 30, dirs["one"], seed) + ["--replicas", "1", "--repl_every", "10"])
     assert _lines(dirs["one"] + "repliter.txt") == ["10", "20", "30"]
     num1, den1 = _lines(dirs["one"] + "replnum.txt"), _lines(dirs["one"] + "replden.txt")
     assert len(num1) == 3 and len(den1) == 3 and all("," not in x for x in num1 + den1)

@@ -9,19 +9,16 @@ adds in; the 8 covers the products and fsum's own rounding.  ovlp and abs_sum ar
 import dataclasses
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import golden_io
+import pair_common as pc
 from fries_amd import fcidump
+from pair_common import SMALL, U, as_map as _as_map, ne_run as _ne_run, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -53
-SMALL = dict(epsilon=0.01, vec_nonz=100, mat_nonz=100, max_dets=1000, seed=1, distribution="HB_unnorm")
-NE_PAIR = dict(epsilon=0.01, vec_nonz=150, mat_nonz=150, max_dets=4000, target_norm=100.0, distribution="HB_unnorm")
 # the geometry of csrc/rdm1_plan.hpp: positions per workgroup, partial matrices one workgroup of the fold adds
 RD_BPOS, RD_FAN = 256, 64
 
@@ -32,17 +29,7 @@ def Engine():
     return FriEngine
 
 
-def _ne_run():
-    r = golden_io.manifest()["runs"]["ne_m2000_unnorm"]
-    return dict(epsilon=r["epsilon"], vec_nonz=r["vec_nonz"], mat_nonz=r["mat_nonz"], max_dets=r["max_dets"], target_norm=r["target_norm"],
-                initiator=r["initiator"], seed=r["seed"], distribution=r["distribution"])
-
-
 # ------------------------------------------------------------------ the host reference
-def _as_map(dets, vals):
-    return {int(d): float(v) for d, v in zip(dets, vals) if v != 0.0}
-
-
 def _reference(a, b, n_orb):
     """gamma(a, b) term by term (a enumerates, b is looked up): per bin the fsum, the sum of magnitudes and the number of terms"""
     terms = {}
@@ -100,10 +87,6 @@ def _check(tag, res, ref):
     assert abs(res.abs_sum - ref["abs_sum"]) <= ref["bound_abs"], tag
 
 
-def _same_bits(x, y):
-    return np.array_equal(x.gamma, y.gamma) and x[1:] == y[1:]
-
-
 def _check_trace(tag, res, ref, n_elec):
     tr, bound = float(np.trace(res.gamma)), float(np.trace(ref["bound"])) + n_elec * ref["bound_ov"] + 2 * n_elec * U * abs(n_elec * ref["ovlp"])
     print(f"{tag}: trace {tr!r} n_elec * ovlp {n_elec * res.ovlp!r} bound {bound:.3e}")
@@ -115,17 +98,7 @@ def test_whole_space_min4(Engine, mols):
     """2 electrons in 4 orbitals, C1: all 16 determinants in both vectors, in different orders, two exact zeros each (the construction of
     test_gpu_hdot.py::test_whole_space_min4)."""
     mol = mols("MIN4")
-    dets = np.array([(1 << p) | (1 << (mol.n_orb + q)) for p in range(4) for q in range(4)], dtype=np.uint64)
-    rng = np.random.RandomState(20251)
-    ea, eb = Engine(mol), Engine(mol)
-    for e in (ea, eb):
-        e.setup(epsilon=0.01, vec_nonz=50, mat_nonz=50, max_dets=1000, seed=3, distribution="HB_unnorm")
-    da, db = dets[rng.permutation(16)], dets[rng.permutation(16)]
-    va, vb = rng.standard_normal(16), rng.standard_normal(16)
-    va[[3, 11]] = 0.0
-    vb[[0, 7]] = 0.0
-    ea.vec_load(da, va)
-    eb.vec_load(db, vb)
+    ea, eb, _, (da, va), (db, vb) = pc.min4_pair(Engine, mol, 20251)
     a, b = _as_map(da, va), _as_map(db, vb)
     r_ab, r_ba, r_aa = ea.rdm1(eb), eb.rdm1(ea), ea.rdm1()
     ref_ab = _reference(a, b, mol.n_orb)
@@ -150,11 +123,7 @@ def test_sparse_vectors_with_holes(Engine, mols):
     """Two Ne runs (seeds 1 and 2), 25 iterations at vec_nonz = mat_nonz = 150: compressed vectors with released positions and a hash
     table that has seen deletions; most targets are not in the other vector."""
     mol = mols("Ne")
-    ea, eb = Engine(mol), Engine(mol)
-    ea.setup(seed=1, **NE_PAIR)
-    eb.setup(seed=2, **NE_PAIR)
-    ea.iterate(25)
-    eb.iterate(25)
+    ea, eb = pc.ne_pair(Engine, mol)
     (da, va), (db, vb) = ea.vector(), eb.vector()
     a, b = _as_map(da, va), _as_map(db, vb)
     assert len(a) < da.size or len(b) < db.size or ea.vec_info()[2] + eb.vec_info()[2] > 0, "no released position in either vector"
@@ -260,11 +229,7 @@ def test_tie_to_h_dot(Engine, mols):
     of the Ne runs' determinants), so that the heat-bath tables are never used."""
     mol = mols("Ne")
     one_body = dataclasses.replace(mol, eris=np.zeros_like(mol.eris))
-    src_a, src_b = Engine(mol), Engine(mol)
-    src_a.setup(seed=1, **NE_PAIR)
-    src_b.setup(seed=2, **NE_PAIR)
-    src_a.iterate(25)
-    src_b.iterate(25)
+    src_a, src_b = pc.ne_pair(Engine, mol)
     (da, va), (db, vb) = src_a.vector(), src_b.vector()
     src_a.close()
     src_b.close()
@@ -337,123 +302,28 @@ def test_against_the_reference_one_elec_op(Engine, mols):
 
 
 # ------------------------------------------------------------------ 7. refusals
-def _refused(a, b, match):
-    na, nb = a.kernel_launches, b.kernel_launches
-    with pytest.raises(RuntimeError, match=match) as ex:
-        a.rdm1(b)
-    assert "fries_rdm1" in str(ex.value)
-    assert (a.kernel_launches, b.kernel_launches) == (na, nb)
+def _rdm1(a, b):
+    return a.rdm1(b)
 
 
 def test_refusals_launch_nothing(Engine, mols):
-    import ctypes as C
-    from fries_amd.comm import LocalGroup
     from fries_amd.engine import Rdm1Result
     mol = mols("Ne")
     plain = Engine(mol)
     plain.setup(**SMALL)
-    # null arguments
-    g, r = np.zeros((mol.n_orb, mol.n_orb)), Rdm1Result()
-    n0 = plain.kernel_launches
-    for args in ((None, plain.h, g.ctypes.data_as(C.c_void_p), C.byref(r)), (plain.h, None, g.ctypes.data_as(C.c_void_p), C.byref(r)),
-                 (plain.h, plain.h, None, C.byref(r)), (plain.h, plain.h, g.ctypes.data_as(C.c_void_p), None)):
-        assert plain.lib.fries_rdm1(*args) != 0
-        assert "fries_rdm1: null argument" in plain.lib.fries_last_error().decode()
-    assert plain.kernel_launches == n0
-    # a communicator, even of one rank
-    grp = LocalGroup(1, SMALL["mat_nonz"])
-    ranked = Engine(mol, comm=grp.comm(0, 0))
-    ranked.setup(**SMALL)
-    _refused(plain, ranked, "communicator")
-    _refused(ranked, plain, "communicator")
-    _refused(ranked, ranked, "communicator")
-    ranked.close()
-    grp.destroy()
-    # Hubbard-Holstein
-    r = golden_io.manifest()["hh_runs"]["hh_l6_m2000"]
-    hh = Engine(None)
-    hh.setup_hh(n_elec=r["n_elec"], n_sites=r["n_sites"], eps=r["eps"], U=r["U"], omega=r["omega"], g=r["g"], gs_energy=r["gs_energy"],
-                vec_nonz=100, max_dets=1000, target_norm=r["target_norm"], initiator=r["initiator"], seed=r["seed"])
-    _refused(hh, hh, "Hubbard-Holstein")
-    _refused(plain, hh, "Hubbard-Holstein")
-    hh.close()
-    # no molecule; no solution vector yet
-    empty = Engine(None)
-    _refused(plain, empty, "fries_set_molecule")
-    empty.close()
-    bare = Engine(mol)
-    _refused(plain, bare, "solution vector")
-    _refused(bare, plain, "solution vector")
-    bare.close()
-    # different molecules: another shape; the same shape with other irreps
-    other = Engine(mols("H2O"))
-    other.setup(**SMALL)
-    _refused(plain, other, "different molecules")
-    _refused(other, plain, "different molecules")
-    other.close()
-    relabelled = Engine(dataclasses.replace(mol, irreps=np.zeros_like(mol.irreps)))
-    relabelled.setup(**SMALL)
-    _refused(plain, relabelled, "irreps")
-    relabelled.close()
-    # the same shape with other integrals is NOT refused: hf_en plays no part
-    shifted = Engine(fcidump.synthetic("Ne", seed=777))
-    shifted.setup(**SMALL)
-    assert shifted.hf_energy != plain.hf_energy
-    assert _same_bits(plain.rdm1(shifted), plain.rdm1())        # (both hold 100 x the Hartree-Fock determinant)
-    shifted.close()
-    # time-reversal vectors, on either side
-    flipped = Engine(mol)
-    flipped.setup(**SMALL)
-    for sp in (1, -1):
-        flipped.set_spin_parity(sp)
-        _refused(plain, flipped, "spin_parity")
-        _refused(flipped, plain, "spin_parity")
-        _refused(flipped, flipped, "spin_parity")
-    flipped.set_spin_parity(0)
-    assert _same_bits(plain.rdm1(flipped), plain.rdm1())
-    flipped.close()
+    pc.check_common_refusals(Engine, mols, plain, _rdm1, "fries_rdm1", Rdm1Result, np.zeros((mol.n_orb, mol.n_orb)))
+    pc.check_density_matrix_refusals(Engine, plain, _rdm1, "fries_rdm1")
     plain.close()
 
 
 # ------------------------------------------------------------------ 8. the estimator reads, and only reads
 def test_estimator_does_not_disturb_the_run(Engine, mols):
-    mol = mols("Ne")
-    par = _ne_run()
-    quiet_a, quiet_b, probed_a, probed_b = (Engine(mol) for _ in range(4))
-    for e, seed in ((quiet_a, par["seed"]), (quiet_b, par["seed"] + 1), (probed_a, par["seed"]), (probed_b, par["seed"] + 1)):
-        e.setup(**dict(par, seed=seed))
-    want = [quiet_a.iterate(20), quiet_b.iterate(20)]
-    first = [probed_a.iterate(10), probed_b.iterate(10)]
-    res = probed_a.rdm1(probed_b)
-    assert res.n_hits > 0 and probed_b.rdm1(probed_a).n_hits == res.n_hits and probed_a.rdm1().n_src > 0
-    got = [np.concatenate([first[0], probed_a.iterate(10)]), np.concatenate([first[1], probed_b.iterate(10)])]
-    for k, (q, p) in enumerate(((quiet_a, probed_a), (quiet_b, probed_b))):
-        assert want[k].tobytes() == got[k].tobytes(), k
-        (dq, vq), (dp, vp) = q.vector(), p.vector()
-        assert dq.tobytes() == dp.tobytes() and vq.tobytes() == vp.tobytes(), k       # (every byte: more than a digest)
-    for e in (quiet_a, quiet_b, probed_a, probed_b):
-        e.close()
+    pc.check_run_undisturbed(Engine, mols("Ne"), _rdm1)
 
 
 # ------------------------------------------------------------------ 9. device memory
 def test_rdm1_returns_its_device_memory(Engine, mols):
-    """fries_rdm1's partial matrices come from a stack DevMem: added to the create / set up / iterate / close cycle of
-    tests/test_gpu_memory.py, that test's bound keeps holding (the means of test_gpu_hdot.py::test_estimator_returns_its_device_memory)."""
-    import test_gpu_memory as tm
-
-    def cycle(kind, mol):
-        a, b = Engine(mol), Engine(mol)
-        a.setup(seed=1, **tm.NE)
-        b.setup(seed=2, **tm.NE)
-        a.iterate(3)
-        b.iterate(3)
-        assert a.rdm1(b).n_src > 0 and b.rdm1().n_src > 0
-        a.close()
-        b.close()
-
-    lost = tm.lost_bytes("frisys", mols("Ne"), cycle)
-    print(f"{lost} bytes of free device memory lost over {tm.N_CYCLES} cycles with fries_rdm1; bound {tm.TOLERANCE['frisys']}")
-    assert lost <= tm.TOLERANCE["frisys"]
+    pc.check_device_memory_returned(Engine, mols("Ne"), _rdm1, "fries_rdm1")
 
 
 # ------------------------------------------------------------------ 10. FriReplicas
@@ -494,39 +364,6 @@ def test_replicas_pair_rdm1(Engine, mols):
 
 
 # ------------------------------------------------------------------ 11. the command line
-def _cmd(exe, fc, mol, par, n_it, out, seed):
-    return [exe, "--fcidump_path", fc, "--point_group", mol.point_group, "--distribution", par["distribution"], "--vec_nonz", str(par["vec_nonz"]),
-            "--mat_nonz", str(par["mat_nonz"]), "--max_dets", str(par["max_dets"]), "--target", repr(par["target_norm"]), "--initiator", repr(par["initiator"]),
-            "--epsilon", repr(par["epsilon"]), "--max_iter", str(n_it), "--result_dir", out, "--seed", str(seed), "--precision", "17"]
-
-
-def _saved_vector(out, mol):
-    nb = (2 * mol.n_orb + 7) // 8
-    raw = np.fromfile(out + "dets0.dat", dtype=np.uint8)
-    n_saved = raw.size // nb
-    vals = np.fromfile(out + "vals0.dat", dtype=np.float64)
-    dets = np.zeros(n_saved, dtype=np.uint64)
-    for b in range(nb):
-        dets |= raw.reshape(n_saved, nb)[:, b].astype(np.uint64) << np.uint64(8 * b)
-    vals = vals[:n_saved]
-    return dets[vals != 0], vals[vals != 0]
-
-
-def _run(cmd):
-    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0 and "Exception" not in res.stderr, res.stderr[-3000:]
-
-
-def _tree(top):
-    out = {}
-    for dp, _, fs in os.walk(top):
-        for f in fs:
-            p = os.path.join(dp, f)
-            with open(p, "rb") as fh:
-                out[os.path.relpath(p, top)] = fh.read()
-    return out
-
-
 def test_command_line_repl_rdm1(Engine, mols, tmp_path):
     from fries_amd import build
     mol = mols("Ne")
@@ -538,9 +375,9 @@ def test_command_line_repl_rdm1(Engine, mols, tmp_path):
     for d in dirs.values():
         os.makedirs(d)
     repl = ["--replicas", "2", "--repl_every", "10"]
-    _run(_cmd(build.DRIVER, fc, mol, par, 20, dirs["with"], seed) + repl + ["--repl_rdm1", "1"])
-    _run(_cmd(build.DRIVER, fc, mol, par, 20, dirs["without"], seed) + repl)
-    with_, without = _tree(dirs["with"]), _tree(dirs["without"])
+    pc.run(pc.cmd(build.DRIVER, fc, mol, par, 20, dirs["with"], seed) + repl + ["--repl_rdm1", "1"])
+    pc.run(pc.cmd(build.DRIVER, fc, mol, par, 20, dirs["without"], seed) + repl)
+    with_, without = pc.tree(dirs["with"]), pc.tree(dirs["without"])
     assert sorted(set(with_) - set(without)) == ["replrdm1.txt"] and not set(without) - set(with_)
     assert {"repliter.txt", "replnum.txt", "replden.txt", os.path.join("replica0", "dets0.dat"), os.path.join("replica1", "projnum.txt")} <= set(without)
     for name, blob in without.items():
@@ -554,7 +391,7 @@ def test_command_line_repl_rdm1(Engine, mols, tmp_path):
     for r in range(2):
         e = Engine(mol)
         e.setup(**dict(par, seed=seed + r))
-        d, v = _saved_vector(dirs["with"] + f"replica{r}/", mol)
+        d, v = pc.saved_vector(dirs["with"] + f"replica{r}/", mol)
         e.vec_load(d, v)
         engs.append(e)
         maps.append(_as_map(d, v))
@@ -567,8 +404,8 @@ def test_command_line_repl_rdm1(Engine, mols, tmp_path):
     assert np.all(np.abs(printed - res.gamma) <= 2 * ref["bound"])
     assert abs(np.trace(printed) - mol.n_elec * float(with_["replden.txt"].decode().split()[-1])) <= 2 * (float(np.trace(ref["bound"])) + mol.n_elec * ref["bound_ov"]) + 4 * mol.n_elec * U * abs(np.trace(printed))
     # one replica: the pair (0, 0)
-    _run(_cmd(build.DRIVER, fc, mol, par, 20, dirs["one"], seed) + ["--replicas", "1", "--repl_every", "10", "--repl_rdm1", "1"])
-    one = _tree(dirs["one"])["replrdm1.txt"].decode().split("\n")
+    pc.run(pc.cmd(build.DRIVER, fc, mol, par, 20, dirs["one"], seed) + ["--replicas", "1", "--repl_every", "10", "--repl_rdm1", "1"])
+    one = pc.tree(dirs["one"])["replrdm1.txt"].decode().split("\n")
     assert len(one) == 3 and one[-1] == ""
     self_printed = np.array([float(x) for x in one[1].split(",")]).reshape(mol.n_orb, mol.n_orb)
     _check_gamma("one replica", self_printed, _reference(maps[0], maps[0], mol.n_orb))

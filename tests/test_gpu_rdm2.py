@@ -9,20 +9,18 @@ the terms are summed with math.fsum.  With u = 2**-53 every term is one rounded 
 in; the 8 covers the products, fsum's own rounding and the one addition of the two halves of a bin (the device accumulates one of the
 records (p,q,r,s) / (r,s,p,q) of every term and adds the matrix to its pair transpose).  ovlp and abs_sum are bounded the same way.
 Worst cases, not measured."""
-import dataclasses
 import math
 import os
 
 import numpy as np
 import pytest
 
-import golden_io
+import pair_common as pc
 import test_gpu_rdm1 as t1
 from fries_amd import fcidump
+from pair_common import SMALL, U, as_map as _as_map, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
-U = 2.0 ** -53
-SMALL, NE_PAIR = t1.SMALL, t1.NE_PAIR
 R2_BPOS, R2_WPOS = 32, 8          # the geometry of csrc/rdm2_plan.hpp: positions per workgroup and per wave
 
 
@@ -30,9 +28,6 @@ R2_BPOS, R2_WPOS = 32, 8          # the geometry of csrc/rdm2_plan.hpp: position
 def Engine():
     from fries_amd.engine import FriEngine
     return FriEngine
-
-
-_as_map = t1._as_map
 
 
 def _below(d, x):
@@ -140,10 +135,6 @@ def _check(tag, res, ref):
     assert np.array_equal(res.gamma2, res.gamma2.transpose(2, 3, 0, 1)), tag
 
 
-def _same_bits(x, y):
-    return np.array_equal(x.gamma2, y.gamma2) and x[1:] == y[1:]
-
-
 def _check_full_trace(tag, res, ref, n_elec):
     """sum_pr Gamma[p,p,r,r] = n_elec (n_elec - 1) <a|b>: the bins' bounds, the overlap's bound times the factor, and 2 u per addition of this
     test's own sum of n_orb^2 bins"""
@@ -174,17 +165,7 @@ def _all_checks(ea, eb, a, b, n_orb, n_elec):
 def test_whole_space_min4(Engine, mols):
     """2 electrons in 4 orbitals, C1: all 16 determinants in both vectors, in different orders, two exact zeros each"""
     mol = mols("MIN4")
-    dets = np.array([(1 << p) | (1 << (mol.n_orb + q)) for p in range(4) for q in range(4)], dtype=np.uint64)
-    rng = np.random.RandomState(20252)
-    ea, eb = Engine(mol), Engine(mol)
-    for e in (ea, eb):
-        e.setup(epsilon=0.01, vec_nonz=50, mat_nonz=50, max_dets=1000, seed=3, distribution="HB_unnorm")
-    da, db = dets[rng.permutation(16)], dets[rng.permutation(16)]
-    va, vb = rng.standard_normal(16), rng.standard_normal(16)
-    va[[3, 11]] = 0.0
-    vb[[0, 7]] = 0.0
-    ea.vec_load(da, va)
-    eb.vec_load(db, vb)
+    ea, eb, _, (da, va), (db, vb) = pc.min4_pair(Engine, mol, 20252)
     r_ab, ref = _all_checks(ea, eb, _as_map(da, va), _as_map(db, vb), mol.n_orb, mol.n_elec)
     assert r_ab.gamma2.shape == (4, 4, 4, 4) and r_ab.n_src == 14 and r_ab.n_terms == 14 * (2 * 1 * 3 + 0 + 1 * 9)
     assert set(ref["classes"]) == {"diagonal", "single direct", "double opposite"}      # no same-spin pair in this space
@@ -193,13 +174,7 @@ def test_whole_space_min4(Engine, mols):
 
 
 # ------------------------------------------------------------------ 2. compressed vectors with holes
-def _ne_pair(Engine, mol):
-    ea, eb = Engine(mol), Engine(mol)
-    ea.setup(seed=1, **NE_PAIR)
-    eb.setup(seed=2, **NE_PAIR)
-    ea.iterate(25)
-    eb.iterate(25)
-    return ea, eb
+_ne_pair = pc.ne_pair
 
 
 def test_sparse_vectors_with_holes(Engine, mols):
@@ -311,7 +286,7 @@ def test_several_chunks(Engine, mols, monkeypatch):
     monkeypatch.setenv("FRIES_RDM2_RECORDS", str(cap - 1))
     tight = Engine(mol)
     monkeypatch.delenv("FRIES_RDM2_RECORDS")
-    tight.setup(seed=1, **NE_PAIR)
+    tight.setup(seed=1, **pc.NE_PAIR)
     tight.iterate(25)
     for e in (ca, tight):
         d, v = e.vector()
@@ -400,130 +375,35 @@ def test_spin_squared_of_the_open_shell_pair(Engine, mols):
 
 
 # ------------------------------------------------------------------ 6. refusals
-def _refused(a, b, match):
-    na, nb = a.kernel_launches, b.kernel_launches
-    with pytest.raises(RuntimeError, match=match) as ex:
-        a.rdm2(b)
-    assert "fries_rdm2" in str(ex.value)
-    assert (a.kernel_launches, b.kernel_launches) == (na, nb)
+def _rdm2(a, b):
+    return a.rdm2(b)
 
 
 def test_refusals_launch_nothing(Engine, mols):
-    import ctypes as C
-    from fries_amd.comm import LocalGroup
     from fries_amd.engine import Rdm2Result
     mol = mols("Ne")
     plain = Engine(mol)
     plain.setup(**SMALL)
-    # null arguments
-    g, r = np.zeros((mol.n_orb,) * 4), Rdm2Result()
-    n0 = plain.kernel_launches
-    for args in ((None, plain.h, g.ctypes.data_as(C.c_void_p), C.byref(r)), (plain.h, None, g.ctypes.data_as(C.c_void_p), C.byref(r)),
-                 (plain.h, plain.h, None, C.byref(r)), (plain.h, plain.h, g.ctypes.data_as(C.c_void_p), None)):
-        assert plain.lib.fries_rdm2(*args) != 0
-        assert "fries_rdm2: null argument" in plain.lib.fries_last_error().decode()
-    assert plain.kernel_launches == n0
-    # a communicator, even of one rank
-    grp = LocalGroup(1, SMALL["mat_nonz"])
-    ranked = Engine(mol, comm=grp.comm(0, 0))
-    ranked.setup(**SMALL)
-    _refused(plain, ranked, "communicator")
-    _refused(ranked, plain, "communicator")
-    _refused(ranked, ranked, "communicator")
-    ranked.close()
-    grp.destroy()
-    # Hubbard-Holstein
-    r = golden_io.manifest()["hh_runs"]["hh_l6_m2000"]
-    hh = Engine(None)
-    hh.setup_hh(n_elec=r["n_elec"], n_sites=r["n_sites"], eps=r["eps"], U=r["U"], omega=r["omega"], g=r["g"], gs_energy=r["gs_energy"],
-                vec_nonz=100, max_dets=1000, target_norm=r["target_norm"], initiator=r["initiator"], seed=r["seed"])
-    _refused(hh, hh, "Hubbard-Holstein")
-    _refused(plain, hh, "Hubbard-Holstein")
-    hh.close()
-    # no molecule; no solution vector yet
-    empty = Engine(None)
-    _refused(plain, empty, "fries_set_molecule")
-    empty.close()
-    bare = Engine(mol)
-    _refused(plain, bare, "solution vector")
-    _refused(bare, plain, "solution vector")
-    bare.close()
-    # different molecules: another shape; the same shape with other irreps
-    other = Engine(mols("H2O"))
-    other.setup(**SMALL)
-    _refused(plain, other, "different molecules")
-    _refused(other, plain, "different molecules")
-    other.close()
-    relabelled = Engine(dataclasses.replace(mol, irreps=np.zeros_like(mol.irreps)))
-    relabelled.setup(**SMALL)
-    _refused(plain, relabelled, "irreps")
-    relabelled.close()
-    # the same shape with other integrals is NOT refused: hf_en is not compared
-    shifted = Engine(fcidump.synthetic("Ne", seed=777))
-    shifted.setup(**SMALL)
-    assert shifted.hf_energy != plain.hf_energy
-    assert _same_bits(plain.rdm2(shifted), plain.rdm2())        # (both hold 100 x the Hartree-Fock determinant)
-    shifted.close()
-    # time-reversal vectors, on either side
-    flipped = Engine(mol)
-    flipped.setup(**SMALL)
-    for sp in (1, -1):
-        flipped.set_spin_parity(sp)
-        _refused(plain, flipped, "spin_parity")
-        _refused(flipped, plain, "spin_parity")
-        _refused(flipped, flipped, "spin_parity")
-    flipped.set_spin_parity(0)
-    assert _same_bits(plain.rdm2(flipped), plain.rdm2())
-    flipped.close()
+    pc.check_common_refusals(Engine, mols, plain, _rdm2, "fries_rdm2", Rdm2Result, np.zeros((mol.n_orb,) * 4))
+    pc.check_density_matrix_refusals(Engine, plain, _rdm2, "fries_rdm2")
     plain.close()
 
 
 # ------------------------------------------------------------------ 7. the estimator reads, and only reads
 def test_estimator_does_not_disturb_the_run(Engine, mols):
-    mol = mols("Ne")
-    par = t1._ne_run()
-    quiet_a, quiet_b, probed_a, probed_b = (Engine(mol) for _ in range(4))
-    for e, seed in ((quiet_a, par["seed"]), (quiet_b, par["seed"] + 1), (probed_a, par["seed"]), (probed_b, par["seed"] + 1)):
-        e.setup(**dict(par, seed=seed))
-    want = [quiet_a.iterate(20), quiet_b.iterate(20)]
-    first = [probed_a.iterate(10), probed_b.iterate(10)]
-    res = probed_a.rdm2(probed_b)
-    assert res.n_hits > 0 and probed_b.rdm2(probed_a).n_hits == res.n_hits and probed_a.rdm2().n_src > 0
-    got = [np.concatenate([first[0], probed_a.iterate(10)]), np.concatenate([first[1], probed_b.iterate(10)])]
-    for k, (q, p) in enumerate(((quiet_a, probed_a), (quiet_b, probed_b))):
-        assert want[k].tobytes() == got[k].tobytes(), k
-        (dq, vq), (dp, vp) = q.vector(), p.vector()
-        assert dq.tobytes() == dp.tobytes() and vq.tobytes() == vp.tobytes(), k
-    for e in (quiet_a, quiet_b, probed_a, probed_b):
-        e.close()
+    pc.check_run_undisturbed(Engine, mols("Ne"), _rdm2)
 
 
 # ------------------------------------------------------------------ 8. device memory
 def test_rdm2_returns_its_device_memory(Engine, mols):
-    """fries_rdm2's counters, matrix and records come from a stack DevMem: added to the create / set up / iterate / close cycle of
-    tests/test_gpu_memory.py, that test's bound keeps holding."""
-    import test_gpu_memory as tm
-
-    def cycle(kind, mol):
-        a, b = Engine(mol), Engine(mol)
-        a.setup(seed=1, **tm.NE)
-        b.setup(seed=2, **tm.NE)
-        a.iterate(3)
-        b.iterate(3)
-        assert a.rdm2(b).n_src > 0 and b.rdm2().n_src > 0
-        a.close()
-        b.close()
-
-    lost = tm.lost_bytes("frisys", mols("Ne"), cycle)
-    print(f"{lost} bytes of free device memory lost over {tm.N_CYCLES} cycles with fries_rdm2; bound {tm.TOLERANCE['frisys']}")
-    assert lost <= tm.TOLERANCE["frisys"]
+    pc.check_device_memory_returned(Engine, mols("Ne"), _rdm2, "fries_rdm2")
 
 
 # ------------------------------------------------------------------ 9. FriReplicas
 def test_replicas_pair_rdm2(Engine, mols):
     from fries_amd.replicas import FriReplicas
     mol = mols("Ne")
-    par = t1._ne_run()
+    par = pc.ne_run()
     seed = par.pop("seed")
     reps = FriReplicas(mol, 3, seed, **par)
     reps.iterate(20)
@@ -557,7 +437,7 @@ def test_replicas_pair_rdm2(Engine, mols):
 def test_command_line_repl_rdm2(Engine, mols, tmp_path):
     from fries_amd import build
     mol = mols("Ne")
-    par = t1._ne_run()
+    par = pc.ne_run()
     seed = 20250215
     n = mol.n_orb
     fc = str(tmp_path / "mol.FCIDUMP")
@@ -566,9 +446,9 @@ def test_command_line_repl_rdm2(Engine, mols, tmp_path):
     for d in dirs.values():
         os.makedirs(d)
     repl = ["--replicas", "2", "--repl_every", "10"]
-    t1._run(t1._cmd(build.DRIVER, fc, mol, par, 20, dirs["with"], seed) + repl + ["--repl_rdm2", "1"])
-    t1._run(t1._cmd(build.DRIVER, fc, mol, par, 20, dirs["without"], seed) + repl)
-    with_, without = t1._tree(dirs["with"]), t1._tree(dirs["without"])
+    pc.run(pc.cmd(build.DRIVER, fc, mol, par, 20, dirs["with"], seed) + repl + ["--repl_rdm2", "1"])
+    pc.run(pc.cmd(build.DRIVER, fc, mol, par, 20, dirs["without"], seed) + repl)
+    with_, without = pc.tree(dirs["with"]), pc.tree(dirs["without"])
     assert sorted(set(with_) - set(without)) == ["replrdm2.dat", "replrdm2e.txt"] and not set(without) - set(with_)
     for name, blob in without.items():
         assert with_[name] == blob, name
@@ -578,7 +458,7 @@ def test_command_line_repl_rdm2(Engine, mols, tmp_path):
     # the last block against the reference built from the two final checkpoints
     maps = []
     for r in range(2):
-        d, v = t1._saved_vector(dirs["with"] + f"replica{r}/", mol)
+        d, v = pc.saved_vector(dirs["with"] + f"replica{r}/", mol)
         maps.append(_as_map(d, v))
     ref2, ref1 = _reference(maps[0], maps[1], n), t1._reference(maps[0], maps[1], n)
     _check_gamma("replrdm2.dat, last block", last, ref2)
@@ -607,8 +487,8 @@ def test_command_line_repl_rdm2(Engine, mols, tmp_path):
     print(f"replrdm2e.txt last value {e_last!r}; replnum / replden + hf {num / den + hf!r}; difference {abs(e_last - (num / den + hf)):.3e}; allowance {allow:.3e}")
     assert abs(e_last - (num / den + hf)) <= allow
     # one replica: the pair (0, 0)
-    t1._run(t1._cmd(build.DRIVER, fc, mol, par, 20, dirs["one"], seed) + ["--replicas", "1", "--repl_every", "10", "--repl_rdm2", "1"])
-    one = t1._tree(dirs["one"])
+    pc.run(pc.cmd(build.DRIVER, fc, mol, par, 20, dirs["one"], seed) + ["--replicas", "1", "--repl_every", "10", "--repl_rdm2", "1"])
+    one = pc.tree(dirs["one"])
     self_blocks = np.frombuffer(one["replrdm2.dat"], dtype="<f8")
     assert self_blocks.size == 2 * n ** 4 and len(one["replrdm2e.txt"].decode().split("\n")) == 3
     _check_gamma("one replica", self_blocks[n ** 4:].reshape((n,) * 4), _reference(maps[0], maps[0], n))

@@ -3,7 +3,7 @@
 Two programs drive FRI through DistVec / Adder / HBCompressSys / apply_HBPP_sys / find_preserve / sys_comp / adjust_shift exactly as
 FRIES_bin/frisys_mol.cpp does:
 
-  * tests/cpp/frisys_mol_ref_api -- a test program written against include/FRIES with a --seed option and 17-digit output;
+  * fries_amd/frisys_mol_ref_api (tests/cpp/frisys_mol_ref_api.cpp) -- a test program written against include/FRIES with a --seed option and 17-digit output;
   * oracle/_ref/frisys_mol_refsrc_on_hip -- the reference's OWN frisys_mol.cpp, compiled where it lies in /root/reference with only the
     include path changed (oracle/Makefile `refdrv`, built by __graft_entry__.build() in the container; the binary travels to the GPU
     box like the other files of oracle/_ref).  It seeds from the clock, so the test pins std::chrono::system_clock::now() with an

@@ -30,5 +30,5 @@ def test_entry_points_are_listed_and_declared():
 
 def test_device_loop_consumer_was_built():
     assert os.path.exists(os.path.join(ROOT, "include", "FRIES", "device_loop.hpp"))
-    assert os.path.exists(build.DEVICE_LOOP_DRIVER), "tests/cpp/frisys_mol_device_loop has not been built"
+    assert os.path.exists(build.DEVICE_LOOP_DRIVER), "frisys_mol_device_loop (tests/cpp/frisys_mol_device_loop.cpp) has not been built"
     assert os.access(build.DEVICE_LOOP_DRIVER, os.X_OK)
