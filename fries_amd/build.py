@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfries_hip.so")
-SOURCES = ["hbpp.hip", "vec.hip", "compress.hip", "pivotal.hip", "system.hip", "hdot.hip", "rdm1.hip", "rdm2.hip", "hh.hip", "fciqmc.hip", "frisys.hip", "api.hip", "api_vec.hip", "api_test.hip", "comm_native.hip"]
+SOURCES = ["hbpp.hip", "vec.hip", "compress.hip", "pivotal.hip", "system.hip", "hdot.hip", "rdm1.hip", "rdm2.hip", "snapshot.hip", "hh.hip", "fciqmc.hip", "frisys.hip", "api.hip", "api_vec.hip", "api_test.hip", "comm_native.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wno-unused-value", "-Wno-unused-result"] + os.environ.get("FRIES_EXTRA_HIPCC_FLAGS", "").split()      # (diagnostic builds: -DFR_SEQ_TIMING, -DFR_FKS_CHKDBG)
 
 

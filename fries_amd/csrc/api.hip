@@ -481,3 +481,60 @@ extern "C" int fries_rdm2(fries_ctx *a, fries_ctx *b, double *gamma2, fries_rdm2
         fr_rdm2(&a->c, &b->c, gamma2, out);
     });
 }
+
+// ------------------------------------------------------------------ vector snapshots and the estimators over ranks: snapshot.hip
+// the handles of a shard list as contexts; refuses a null list, a count outside 1 .. FR_MAX_RANKS and a null entry
+static std::vector<FriesCtx *> shard_list(const char *who, fries_ctx *const *h, uint32_t n) {
+    if (!h) throw FriesError(std::string(who) + ": null argument");
+    if (n == 0 || n > FR_MAX_RANKS) throw FriesError(std::string(who) + ": the number of shards must be between 1 and " + std::to_string(FR_MAX_RANKS));
+    std::vector<FriesCtx *> c(n);
+    for (uint32_t k = 0; k < n; k++) {
+        if (!h[k]) throw FriesError(std::string(who) + ": null argument (a shard)");
+        c[k] = &h[k]->c;
+    }
+    return c;
+}
+extern "C" int fries_snapshot_create(fries_snapshot **s, fries_ctx *const *shards, uint32_t n_shards, int device) {
+    return fr_api([&] {
+        if (!s) throw FriesError("fries_snapshot_create: null argument");
+        *s = nullptr;
+        const std::vector<FriesCtx *> c = shard_list("fries_snapshot_create", shards, n_shards);
+        *s = fr_snapshot_create(c.data(), n_shards, device);
+    });
+}
+extern "C" int fries_snapshot_info(const fries_snapshot *s, fries_snapshot_info_t *out) {
+    return fr_api([&] {
+        if (!s || !out) throw FriesError("fries_snapshot_info: null argument");
+        fr_snapshot_info(s, out);
+    });
+}
+extern "C" int fries_snapshot_vector(const fries_snapshot *s, uint64_t *dets, double *vals, uint64_t cap, uint64_t *n) {
+    return fr_api([&] {
+        if (!s) throw FriesError("fries_snapshot_vector: null argument");
+        fr_snapshot_vector(s, dets, vals, cap, n);
+    });
+}
+extern "C" int fries_snapshot_destroy(fries_snapshot *s) {
+    return fr_api([&] { fr_snapshot_destroy(s); });
+}
+extern "C" int fries_h_dot_ranks(fries_ctx *const *a, uint32_t n_a, const fries_snapshot *b, fries_hdot_result *out) {
+    return fr_api([&] {
+        if (!b || !out) throw FriesError("fries_h_dot_ranks: null argument");
+        const std::vector<FriesCtx *> c = shard_list("fries_h_dot_ranks", a, n_a);
+        fr_h_dot_ranks(c.data(), n_a, b, out);
+    });
+}
+extern "C" int fries_rdm1_ranks(fries_ctx *const *a, uint32_t n_a, const fries_snapshot *b, double *gamma, fries_rdm1_result *out) {
+    return fr_api([&] {
+        if (!b || !gamma || !out) throw FriesError("fries_rdm1_ranks: null argument");
+        const std::vector<FriesCtx *> c = shard_list("fries_rdm1_ranks", a, n_a);
+        fr_rdm1_ranks(c.data(), n_a, b, gamma, out);
+    });
+}
+extern "C" int fries_rdm2_ranks(fries_ctx *const *a, uint32_t n_a, const fries_snapshot *b, double *gamma2, fries_rdm2_result *out) {
+    return fr_api([&] {
+        if (!b || !gamma2 || !out) throw FriesError("fries_rdm2_ranks: null argument");
+        const std::vector<FriesCtx *> c = shard_list("fries_rdm2_ranks", a, n_a);
+        fr_rdm2_ranks(c.data(), n_a, b, gamma2, out);
+    });
+}

@@ -345,7 +345,29 @@ void fr_h_diag_vec(FriesCtx *c, double id_fac, double h_fac);
 uint64_t fr_h_offdiag_vec(FriesCtx *c, double h_fac);
 // hdot.hip
 void fr_h_dot(FriesCtx *a, FriesCtx *b, fries_hdot_result *out);
+void fr_h_dot_core(FriesCtx *a, const VecDev &B, uint32_t n_pos, fries_hdot_result *out);      // the *_core: the estimator behind its refusals, B = whatever is probed
 // rdm1.hip
 void fr_rdm1(FriesCtx *a, FriesCtx *b, double *gamma, fries_rdm1_result *out);
+void fr_rdm1_core(const char *who, FriesCtx *a, const VecDev &B, uint32_t n_pos, double *gamma, fries_rdm1_result *out);
 // rdm2.hip
 void fr_rdm2(FriesCtx *a, FriesCtx *b, double *gamma2, fries_rdm2_result *out);
+void fr_rdm2_core(const char *who, FriesCtx *a, const VecDev &B, uint32_t n_pos, double *gamma2, fries_rdm2_result *out);
+// ... and its halves: what the counting pass leaves for the emitting passes (the counters, the matrix and the offsets on the device, the cut)
+struct Rdm2Pass {
+    DevMem tmp;
+    uint32_t n_pos = 0, n_wg = 0; size_t n_waves = 0;
+    double *d_G = nullptr; uint32_t *d_off = nullptr;
+    Rdm2Plan plan;
+};
+void fr_rdm2_count(const char *who, FriesCtx *a, const VecDev &B, uint32_t n_pos, Rdm2Pass &p, double *gamma2, fries_rdm2_result *out);
+void fr_rdm2_refuse(const char *who, const FriesCtx *a, const Rdm2Pass &p, const char *where);
+void fr_rdm2_emit(const char *who, FriesCtx *a, const VecDev &B, Rdm2Pass &p, double *gamma2);
+// snapshot.hip: an immutable copy of column 0 of a (sharded) vector as one look-up table, and the estimators against it with `a` sharded
+struct fries_snapshot;
+fries_snapshot *fr_snapshot_create(FriesCtx *const *shards, uint32_t n_shards, int device);
+void fr_snapshot_info(const fries_snapshot *s, fries_snapshot_info_t *out);
+void fr_snapshot_vector(const fries_snapshot *s, uint64_t *dets, double *vals, uint64_t cap, uint64_t *n);
+void fr_snapshot_destroy(fries_snapshot *s);
+void fr_h_dot_ranks(FriesCtx *const *a, uint32_t n_a, const fries_snapshot *b, fries_hdot_result *out);
+void fr_rdm1_ranks(FriesCtx *const *a, uint32_t n_a, const fries_snapshot *b, double *gamma, fries_rdm1_result *out);
+void fr_rdm2_ranks(FriesCtx *const *a, uint32_t n_a, const fries_snapshot *b, double *gamma2, fries_rdm2_result *out);

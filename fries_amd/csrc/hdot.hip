@@ -102,6 +102,12 @@ void fr_h_dot(FriesCtx *a, FriesCtx *b, fries_hdot_result *out) {
     const uint32_t n_pos = fr_pair_begin("fries_h_dot", a, b);
     if (a->hf_en != b->hf_en) throw FriesError("fries_h_dot: the two contexts differ in hf_en, the offset of the diagonal (different molecules or --ham_shift)");
     if (a->spin_parity != b->spin_parity) throw FriesError("fries_h_dot: the two contexts differ in spin_parity");
+    fr_h_dot_core(a, b->vec, n_pos, out);
+}
+
+// The estimator behind its refusals: the first n_pos positions of `a` against B, of which the kernels read hs, hcap, v0 and cap only
+// (another context's vector, or a snapshot's view); on a's stream, back when the result is on the host.
+void fr_h_dot_core(FriesCtx *a, const VecDev &B, uint32_t n_pos, fries_hdot_result *out) {
     hipStream_t st = a->stream;
     *out = fries_hdot_result{};
     if (n_pos == 0) return;
@@ -112,7 +118,7 @@ void fr_h_dot(FriesCtx *a, FriesCtx *b, fries_hdot_result *out) {
     DevMem tmp;
     double *d_part = tmp.alloc<double>(3 * total);
     unsigned long long *d_cnt = tmp.alloc<unsigned long long>(3 * total);
-    FR_LAUNCH(a, "k_hdot", k_hdot, dim3(n_pos), dim3(FR_BLOCK), a->vec, b->vec, S, n_pos, d_part, d_cnt);
+    FR_LAUNCH(a, "k_hdot", k_hdot, dim3(n_pos), dim3(FR_BLOCK), a->vec, B, S, n_pos, d_part, d_cnt);
     size_t off = 0;
     uint32_t n = n_pos;
     do {

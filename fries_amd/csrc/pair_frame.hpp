@@ -1,10 +1,20 @@
 // What the estimators between the solution vectors of two contexts share (hdot.hip: fr_h_dot / k_hdot, rdm1.hip: fr_rdm1 / k_rdm1,
 // rdm2.hip: fr_rdm2 / k_rdm2_probe): on the host how a call begins, on the device how `b` is looked up.  `who` is the entry point's name.
+// snapshot.hip begins its calls with fr_shards_check and fr_pair_n_pos: there a list of shards stands where one context stands here.
 #pragma once
 #include "ctx.hpp"
 #include <cstring>
+#include <sstream>
 
 // ------------------------------------------------------------------ host
+// a's curr_size, read back on its stream (a copy and a wait, no launch) and checked against the capacity.  w = "<entry point>: "
+static inline uint32_t fr_pair_n_pos(const std::string &w, FriesCtx *a) {
+    uint32_t n_pos = 0;
+    FR_HIP(hipMemcpyAsync(&n_pos, &a->vec.st->curr_size, 4, hipMemcpyDeviceToHost, a->stream));
+    FR_HIP(hipStreamSynchronize(a->stream));
+    if (n_pos > a->vec.cap) throw FriesError(w + "the vector's size exceeds its capacity");
+    return n_pos;
+}
 // Refuses what no such estimator handles -- everything that refuses comes before the first launch --, makes a's stream wait for what
 // b's stream has enqueued so far (`b` is only read: it must have run before the probes start) and reads a's curr_size back.
 // -> n_pos, checked against the capacity; the caller adds its own refusals, zeroes its outputs and leaves at once when n_pos == 0.
@@ -27,11 +37,7 @@ static inline uint32_t fr_pair_begin(const char *who, FriesCtx *a, FriesCtx *b) 
         FR_HIP(hipEventRecord(ev.e, b->stream));
         FR_HIP(hipStreamWaitEvent(a->stream, ev.e, 0));
     }
-    uint32_t n_pos = 0;
-    FR_HIP(hipMemcpyAsync(&n_pos, &a->vec.st->curr_size, 4, hipMemcpyDeviceToHost, a->stream));
-    FR_HIP(hipStreamSynchronize(a->stream));
-    if (n_pos > a->vec.cap) throw FriesError(w + "the vector's size exceeds its capacity");
-    return n_pos;
+    return fr_pair_n_pos(w, a);
 }
 // ... and what the density matrices refuse on top: their kernels split a determinant into two n_orb-bit halves and walk it as it is stored
 static inline uint32_t fr_pair_begin_rdm(const char *who, FriesCtx *a, FriesCtx *b) {
@@ -41,6 +47,34 @@ static inline uint32_t fr_pair_begin_rdm(const char *who, FriesCtx *a, FriesCtx 
     for (const FriesCtx *c : {a, b})
         if (c->spin_parity != 0) throw FriesError(w + "a context with spin_parity != 0 stores one representative per time-reversal pair; unfolding it is out of scope");
     return n_pos;
+}
+// What a list of contexts must be to stand for ONE vector (fries_snapshot_create, the *_ranks estimators; snapshot.hip): molecular contexts
+// with a solution vector that are exactly ranks 0 .. n - 1 of one run, in order, and agree in everything the estimators compare.  A context
+// without a communicator is the one shard of a run of one.  "One run" is decided by what determines a run's content: the rank scramblers
+// (drawn from the seed) and the iteration count -- two groups set up alike and iterated alike hold the same shards, bit for bit.
+static inline void fr_shards_check(const char *who, FriesCtx *const *sh, uint32_t n) {
+    const std::string w = std::string(who) + ": ";
+    for (uint32_t k = 0; k < n; k++) {
+        const FriesCtx *c = sh[k];
+        if (c->hh_mode || c->vec.hh_sites) throw FriesError(w + "a Hubbard-Holstein context is not a molecular one (out of scope)");
+        if (!c->d_eris || !c->d_hb) throw FriesError(w + "fries_set_molecule must be called on every context first");
+        if (!c->vec.dets || !c->vec.hs) throw FriesError(w + "every context needs a solution vector (run a setup first)");
+    }
+    const FriesCtx *c0 = sh[0];
+    for (uint32_t k = 0; k < n; k++) {
+        const FriesCtx *c = sh[k];
+        if ((uint32_t)c->n_ranks != n || (uint32_t)c->rank != k) {
+            std::ostringstream os;
+            os << w << "the shards must be ranks 0 .. P - 1 of one run, all of them and in order: entry " << k << " of " << n << " is rank " << c->rank << " of " << c->n_ranks;
+            throw FriesError(os.str());
+        }
+        if (c->n_orb != c0->n_orb || c->n_elec != c0->n_elec) throw FriesError(w + "the shards differ in n_orb or n_elec (different molecules)");
+        if (memcmp(c->h_hb.irrep, c0->h_hb.irrep, c0->n_orb)) throw FriesError(w + "the shards differ in their orbital irreps (different molecules)");
+        if (c->proc_scr != c0->proc_scr) throw FriesError(w + "the shards belong to different runs (their rank scramblers differ)");
+        if (c->iterat != c0->iterat) throw FriesError(w + "the shards belong to different runs or moments of a run (their iteration counts differ)");
+        if (c->hf_en != c0->hf_en) throw FriesError(w + "the shards differ in hf_en, the offset of the diagonal (different molecules or --ham_shift)");
+        if (c->spin_parity != c0->spin_parity) throw FriesError(w + "the shards differ in spin_parity");
+    }
 }
 // refuses, before anything is launched, a scratch array sized from n_pos that the device has no room for
 static inline void fr_need_free(const char *who, size_t bytes, const char *what, uint32_t n_pos) {

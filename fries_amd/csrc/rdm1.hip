@@ -122,6 +122,11 @@ __global__ void __launch_bounds__(FR_BLOCK) k_rdm1_reduce(const double *in_d, co
 
 void fr_rdm1(FriesCtx *a, FriesCtx *b, double *gamma, fries_rdm1_result *out) {
     const uint32_t n_pos = fr_pair_begin_rdm("fries_rdm1", a, b);
+    fr_rdm1_core("fries_rdm1", a, b->vec, n_pos, gamma, out);
+}
+
+// The estimator behind its refusals, as fr_h_dot_core: the first n_pos positions of `a` against B (hs, hcap, v0 and cap are read)
+void fr_rdm1_core(const char *who, FriesCtx *a, const VecDev &B, uint32_t n_pos, double *gamma, fries_rdm1_result *out) {
     hipStream_t st = a->stream;
     const size_t n2 = (size_t)a->n_orb * a->n_orb;
     *out = fries_rdm1_result{};
@@ -129,11 +134,11 @@ void fr_rdm1(FriesCtx *a, FriesCtx *b, double *gamma, fries_rdm1_result *out) {
     if (n_pos == 0) return;
     // the levels of the fold back to back; sized from n_pos and checked against what the device has left before anything is launched
     const Rdm1Plan plan = fr_rdm1_plan(n_pos, a->n_orb);
-    fr_need_free("fries_rdm1", plan.bytes(), "the partial matrices", n_pos);
+    fr_need_free(who, plan.bytes(), "the partial matrices", n_pos);
     DevMem tmp;
     double *d_part = tmp.alloc<double>(plan.total_rows * plan.stride);
     unsigned long long *d_cnt = tmp.alloc<unsigned long long>(plan.total_rows * RD_NCNT);
-    FR_LAUNCH(a, "k_rdm1", k_rdm1, dim3(plan.rows[0]), dim3(FR_BLOCK), a->vec, b->vec, a->n_orb, n_pos, d_part, d_cnt);
+    FR_LAUNCH(a, "k_rdm1", k_rdm1, dim3(plan.rows[0]), dim3(FR_BLOCK), a->vec, B, a->n_orb, n_pos, d_part, d_cnt);
     size_t off = 0;
     for (size_t l = 0; l + 1 < plan.rows.size(); l++) {
         const size_t nxt = off + plan.rows[l];

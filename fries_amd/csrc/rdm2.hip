@@ -214,22 +214,39 @@ __global__ void __launch_bounds__(FR_BLOCK) k_r2_fold(const uint32_t *key, uint3
 
 void fr_rdm2(FriesCtx *a, FriesCtx *b, double *gamma2, fries_rdm2_result *out) {
     const uint32_t n_pos = fr_pair_begin_rdm("fries_rdm2", a, b);
+    fr_rdm2_core("fries_rdm2", a, b->vec, n_pos, gamma2, out);
+}
+
+// The estimator behind its refusals, as fr_h_dot_core: the first n_pos positions of `a` against B (hs, hcap, v0 and cap are read);
+// the matrix it returns is already added to its own pair transpose.  In two halves, so that a caller with several enumerating vectors
+// (fr_rdm2_ranks) can run every counting pass and make every capacity refusal before a single record is written.
+void fr_rdm2_core(const char *who, FriesCtx *a, const VecDev &B, uint32_t n_pos, double *gamma2, fries_rdm2_result *out) {
+    Rdm2Pass p;
+    fr_rdm2_count(who, a, B, n_pos, p, gamma2, out);
+    fr_rdm2_refuse(who, a, p, "");
+    fr_rdm2_emit(who, a, B, p, gamma2);
+}
+
+// The counting pass: zeroes the outputs, probes everything once, adds the waves' scalars and counts into *out and cuts the workgroups
+// into chunks.  A workgroup beyond the capacity is left in p.plan.bad_wg for fr_rdm2_refuse.
+void fr_rdm2_count(const char *who, FriesCtx *a, const VecDev &B, uint32_t n_pos, Rdm2Pass &p, double *gamma2, fries_rdm2_result *out) {
     hipStream_t st = a->stream;
     const uint32_t n = a->n_orb;
     const size_t n2 = (size_t)n * n, n4 = n2 * n2;
     *out = fries_rdm2_result{};
     std::fill(gamma2, gamma2 + n4, 0.0);
+    p.n_pos = n_pos;
     if (n_pos == 0) return;
-    const uint32_t n_wg = fr_blocks(n_pos, R2_BPOS);
-    const size_t n_waves = (size_t)n_wg * R2_WAVES;
+    const uint32_t n_wg = p.n_wg = fr_blocks(n_pos, R2_BPOS);
+    const size_t n_waves = p.n_waves = (size_t)n_wg * R2_WAVES;
     // the counting pass: its arrays and the matrix are sized from n_pos and n_orb and checked before anything is launched
-    fr_need_free("fries_rdm2", n_waves * (R2_NCNT + R2_NSCAL + 1) * 8 + n4 * 8, "the matrix and the counters", n_pos);
-    DevMem tmp;
+    fr_need_free(who, n_waves * (R2_NCNT + R2_NSCAL + 1) * 8 + n4 * 8, "the matrix and the counters", n_pos);
+    DevMem &tmp = p.tmp;
     unsigned long long *d_cnt = tmp.alloc<unsigned long long>(n_waves * R2_NCNT);
     double *d_scal = tmp.alloc<double>(n_waves * R2_NSCAL);
-    double *d_G = tmp.alloc<double>(n4);
-    uint32_t *d_off = tmp.alloc<uint32_t>(n_waves);
-    FR_LAUNCH(a, "k_rdm2_count", (k_rdm2_probe<false>), dim3(n_wg), dim3(FR_BLOCK), a->vec, b->vec, n, n_pos, 0u, d_cnt, d_scal, (const uint32_t *)nullptr, R2Out{});
+    p.d_G = tmp.alloc<double>(n4);
+    p.d_off = tmp.alloc<uint32_t>(n_waves);
+    FR_LAUNCH(a, "k_rdm2_count", (k_rdm2_probe<false>), dim3(n_wg), dim3(FR_BLOCK), a->vec, B, n, n_pos, 0u, d_cnt, d_scal, (const uint32_t *)nullptr, R2Out{});
     std::vector<unsigned long long> hc(n_waves * R2_NCNT);
     std::vector<double> hs(n_waves * R2_NSCAL);
     FR_HIP(hipMemcpyAsync(hc.data(), d_cnt, hc.size() * 8, hipMemcpyDeviceToHost, st));
@@ -242,20 +259,33 @@ void fr_rdm2(FriesCtx *a, FriesCtx *b, double *gamma2, fries_rdm2_result *out) {
         wave_rec[w] = hc[w * R2_NCNT + 3];
         out->ovlp += hs[w * R2_NSCAL]; out->abs_sum += hs[w * R2_NSCAL + 1];
     }
+    p.plan = fr_rdm2_cut(wave_rec.data(), n_wg, a->rdm2_records);
+}
+
+// where = "" or which of several enumerating vectors is meant (" of shard 1")
+void fr_rdm2_refuse(const char *who, const FriesCtx *a, const Rdm2Pass &p, const char *where) {
+    if (p.plan.bad_wg < 0) return;
+    std::ostringstream os;
+    os << who << ": the " << R2_BPOS << " positions from " << (uint64_t)p.plan.bad_wg * R2_BPOS << where << " expand to " << p.plan.bad_need
+       << " bin records, the capacity of a chunk is " << a->rdm2_records << " (FRIES_RDM2_RECORDS)";
+    throw FriesError(os.str());
+}
+
+// Per chunk: emit, sort, sum; then the matrix plus its pair transpose into gamma2 (which fr_rdm2_count zeroed)
+void fr_rdm2_emit(const char *who, FriesCtx *a, const VecDev &B, Rdm2Pass &p, double *gamma2) {
+    if (p.n_pos == 0 || p.plan.total_rec == 0) return;
+    hipStream_t st = a->stream;
+    const uint32_t n = a->n_orb, n_pos = p.n_pos;
+    const size_t n2 = (size_t)n * n, n4 = n2 * n2, n_waves = p.n_waves;
+    const Rdm2Plan &plan = p.plan;
     const uint64_t cap = a->rdm2_records;
-    const Rdm2Plan plan = fr_rdm2_cut(wave_rec.data(), n_wg, cap);
-    if (plan.bad_wg >= 0) {
-        std::ostringstream os;
-        os << "fries_rdm2: the " << R2_BPOS << " positions from " << (uint64_t)plan.bad_wg * R2_BPOS << " expand to " << plan.bad_need
-           << " bin records, the capacity of a chunk is " << cap << " (FRIES_RDM2_RECORDS)";
-        throw FriesError(os.str());
-    }
-    if (plan.total_rec == 0) return;
+    DevMem &tmp = p.tmp;
+    double *d_G = p.d_G; uint32_t *d_off = p.d_off;
     const Rdm2Scratch sc = fr_rdm2_scratch(plan.max_rec);
     if (a->dbg >= 1)
-        fprintf(stderr, "[fries] fries_rdm2: %llu bin records in %zu chunks of at most %llu (capacity %llu), scratch %zu bytes\n", (unsigned long long)plan.total_rec,
+        fprintf(stderr, "[fries] %s: %llu bin records in %zu chunks of at most %llu (capacity %llu), scratch %zu bytes\n", who, (unsigned long long)plan.total_rec,
                 plan.chunks.size(), (unsigned long long)plan.max_rec, (unsigned long long)cap, sc.bytes);
-    fr_need_free("fries_rdm2", sc.bytes, "the bin records", n_pos);
+    fr_need_free(who, sc.bytes, "the bin records", n_pos);
     uint8_t *d_sc = tmp.alloc<uint8_t>(sc.bytes);
     FR_HIP(hipMemsetAsync(d_G, 0, n4 * 8, st));
     FR_HIP(hipMemcpyAsync(d_off, plan.wave_off.data(), n_waves * 4, hipMemcpyHostToDevice, st));
@@ -267,7 +297,7 @@ void fr_rdm2(FriesCtx *a, FriesCtx *b, double *gamma2, fries_rdm2_result *out) {
         uint32_t *pay[2] = {(uint32_t *)(d_sc + sc.pay(0, plan.max_rec)), (uint32_t *)(d_sc + sc.pay(1, plan.max_rec))};
         double *val = (double *)(d_sc + sc.val);
         uint32_t *hist = (uint32_t *)(d_sc + sc.hist);
-        FR_LAUNCH(a, "k_rdm2_emit", (k_rdm2_probe<true>), dim3(ch.wg_hi - ch.wg_lo), dim3(FR_BLOCK), a->vec, b->vec, n, n_pos, ch.wg_lo,
+        FR_LAUNCH(a, "k_rdm2_emit", (k_rdm2_probe<true>), dim3(ch.wg_hi - ch.wg_lo), dim3(FR_BLOCK), a->vec, B, n, n_pos, ch.wg_lo,
                   (unsigned long long *)nullptr, (double *)nullptr, (const uint32_t *)d_off, R2Out{key[0], pay[0], val, nr});
         int src = 0;
         for (int p = 0; p < passes; p++, src ^= 1) {

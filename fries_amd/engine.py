@@ -30,6 +30,7 @@ EXPORTS = [
     "fries_vec_column_download", "fries_vec_column_upload", "fries_vec_column_zero", "fries_vec_diag_download", "fries_vec_dot_list", "fries_vec_add_vecs", "fries_set_det_space", "fries_vec_set_dense", "fries_dense_sizes", "fries_hostcomm_create", "fries_set_vec_scrambler", "fries_hh_comp_sub", "fries_hh_ref_ovlp", "fries_set_spin_parity", "fries_h_offdiag_list",
     "fries_spawn_from_comp", "fries_dense_apply", "fries_dense_norm", "fries_dense_h_count", "fries_comp_download",
     "fries_h_dot", "fries_rdm1", "fries_rdm2",
+    "fries_snapshot_create", "fries_snapshot_info", "fries_snapshot_vector", "fries_snapshot_destroy", "fries_h_dot_ranks", "fries_rdm1_ranks", "fries_rdm2_ranks",
 ]
 
 
@@ -167,6 +168,25 @@ class Rdm2(NamedTuple):
         return float(-n_elec * (n_elec - 4) / 4.0 - 0.5 * np.einsum("pqqp->", self.gamma2) / self.ovlp)
 
 
+class SnapshotInfoStruct(C.Structure):
+    """struct fries_snapshot_info_t"""
+    _fields_ = [("n_entries", C.c_uint64), ("n_shards", C.c_uint32), ("n_slots", C.c_uint32), ("device_bytes", C.c_uint64), ("device", C.c_int32),
+                ("ms_compact", C.c_float), ("ms_copy", C.c_float), ("ms_insert", C.c_float)]
+
+
+class SnapshotInfo(NamedTuple):
+    """fries_snapshot_info's result: the entries, the shards they came from, the look-up table's slots, the device bytes the snapshot owns,
+    its device, and what compaction (summed over the shards), copy and insert took on the device, in milliseconds."""
+    n_entries: int
+    n_shards: int
+    n_slots: int
+    device_bytes: int
+    device: int
+    ms_compact: float
+    ms_copy: float
+    ms_insert: float
+
+
 ITERLOG_DTYPE = np.dtype([("numer", "f8"), ("denom", "f8"), ("shift", "f8"), ("norm", "f8"), ("nkept", "u4"), ("n_nonz", "i4"),
                           ("curr_size", "u4"), ("num_success", "u4"), ("comp_len", "u4", (5,)), ("err", "u4")], align=True)
 
@@ -269,6 +289,13 @@ def load_library() -> C.CDLL:
     lib.fries_h_dot.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(HdotResult)]
     lib.fries_rdm1.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Rdm1Result)]
     lib.fries_rdm2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Rdm2Result)]
+    lib.fries_snapshot_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_uint32, C.c_int]
+    lib.fries_snapshot_info.argtypes = [C.c_void_p, C.POINTER(SnapshotInfoStruct)]
+    lib.fries_snapshot_vector.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.fries_snapshot_destroy.argtypes = [C.c_void_p]
+    lib.fries_h_dot_ranks.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(HdotResult)]
+    lib.fries_rdm1_ranks.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Rdm1Result)]
+    lib.fries_rdm2_ranks.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Rdm2Result)]
     _lib = lib
     return lib
 
@@ -288,6 +315,7 @@ class FriEngine:
         self.h = C.c_void_p()
         self._ck(self.lib.fries_ctx_create(C.byref(self.h), device))
         self.mol = mol
+        self.device = device
         if mol is not None:         # mol=None: a lattice-model run (setup_hh) needs no integrals
             irr = np.ascontiguousarray(mol.irreps, dtype=np.uint8)
             hc = np.ascontiguousarray(mol.h_core, dtype=np.float64)
@@ -752,3 +780,84 @@ class FriEngine:
         v = [C.c_uint64() for _ in range(5)]
         self.lib.fries_counters(self.h, *[C.byref(x) for x in v])
         return dict(zip(("iters", "spawns", "launches", "fks_replays", "stage_elems"), (x.value for x in v)))
+
+
+def _handles(engines):
+    engines = list(engines)
+    return engines, (C.c_void_p * max(len(engines), 1))(*[e.h for e in engines])
+
+
+class VecSnapshot:
+    """A frozen, device-resident copy of column 0 of a vector (fries_snapshot): `shards` are the engines that hold it -- one engine, or
+    ranks 0 .. P - 1 of one sharded run in order, all in this process.  It is the probed side of the estimators over ranks: h_dot,
+    rdm1 and rdm2 take the enumerating vector as its list of shards and return what FriEngine.h_dot / rdm1 / rdm2 return.  The
+    snapshot does not change when its source iterates on; it holds device memory until close()."""
+
+    def __init__(self, shards, device=None):
+        shards, arr = _handles(shards)
+        self.lib = load_library()
+        self.n_orb = shards[0].mol.n_orb if shards and shards[0].mol is not None else 0
+        self.h = C.c_void_p()
+        dev = device if device is not None else (shards[0].device if shards else 0)      # default: the first shard's device
+        self._ck(self.lib.fries_snapshot_create(C.byref(self.h), arr, len(shards), dev))
+
+    def _ck(self, rc):
+        if rc != 0:
+            raise RuntimeError(self.lib.fries_last_error().decode())
+
+    @property
+    def info(self) -> SnapshotInfo:
+        r = SnapshotInfoStruct()
+        self._ck(self.lib.fries_snapshot_info(self.h, C.byref(r)))
+        return SnapshotInfo(int(r.n_entries), int(r.n_shards), int(r.n_slots), int(r.device_bytes), int(r.device), r.ms_compact, r.ms_copy, r.ms_insert)
+
+    def vector(self):
+        """The entries in the snapshot's order: the shards in rank order, each shard's live entries in position order."""
+        n = self.info.n_entries
+        d, v = np.zeros(n, dtype=np.uint64), np.zeros(n)
+        m = C.c_uint64()
+        self._ck(self.lib.fries_snapshot_vector(self.h, _ptr(d), _ptr(v), n, C.byref(m)))
+        return d, v
+
+    def h_dot(self, a_shards) -> HDot:
+        """<a|H|snapshot> and <a|snapshot> (fries_h_dot_ranks): a_shards enumerate, one after the other; no engine among them may be
+        inside another call meanwhile."""
+        shards, arr = _handles(a_shards)
+        r = HdotResult()
+        self._ck(self.lib.fries_h_dot_ranks(arr, len(shards), self.h, C.byref(r)))
+        return HDot(r.h, r.ovlp, r.abs_sum, int(r.n_src), int(r.n_terms), int(r.n_hits))
+
+    def rdm1(self, a_shards) -> Rdm1:
+        """The one-body density matrix <a| ... |snapshot> (fries_rdm1_ranks)"""
+        shards, arr = _handles(a_shards)
+        n = max(self.n_orb, 1)
+        g = np.zeros((n, n))
+        r = Rdm1Result()
+        self._ck(self.lib.fries_rdm1_ranks(arr, len(shards), self.h, _ptr(g), C.byref(r)))
+        return Rdm1(g, r.ovlp, r.abs_sum, int(r.n_src), int(r.n_terms), int(r.n_hits))
+
+    def rdm2(self, a_shards) -> Rdm2:
+        """The two-body density matrix <a| ... |snapshot> (fries_rdm2_ranks), spin-summed, chemists' order"""
+        shards, arr = _handles(a_shards)
+        n = max(self.n_orb, 1)
+        g = np.zeros((n, n, n, n))
+        r = Rdm2Result()
+        self._ck(self.lib.fries_rdm2_ranks(arr, len(shards), self.h, _ptr(g), C.byref(r)))
+        return Rdm2(g, r.ovlp, r.abs_sum, int(r.n_src), int(r.n_terms), int(r.n_hits))
+
+    def close(self):
+        if self.h:
+            self.lib.fries_snapshot_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -308,7 +308,8 @@ int fries_h_offdiag_list(fries_ctx *ctx, const uint64_t *dets, const double *val
  * returns when the result is on the host.  Neither context may be inside another call on another thread while this one runs.
  * Refused with a message and without a launch: a context without a molecule and a solution vector, a Hubbard-Holstein context, a
  * context with a communicator, contexts on different devices, or contexts that differ in n_orb, n_elec, irreps, hf_en or spin_parity.
- * Out of scope: fries_h_dot over ranks (it needs an exchange of the targets), more than one value column per side, Hubbard-Holstein,
+ * Over ranks: fries_h_dot_ranks below, against a fries_snapshot of the probed side (this call keeps refusing a context with a communicator).
+ * Out of scope: more than one value column per side, Hubbard-Holstein,
  * replicas for drivers other than frisys_mol_hip, and a binding in include/FRIES (that facade holds one device-bound vector per
  * process).  fries_frisys_iterate, its launch count and its draws are untouched. */
 typedef struct { double h, ovlp, abs_sum; uint64_t n_src, n_terms, n_hits; } fries_hdot_result;
@@ -333,7 +334,7 @@ int fries_h_dot(fries_ctx *a, fries_ctx *b, fries_hdot_result *out);
  * Refused with a message and without a launch: a null argument, a context without a molecule or without a solution vector, a
  * Hubbard-Holstein context, a context with a communicator, contexts on different devices or that differ in n_orb, n_elec or irreps, and
  * spin_parity != 0 on either side (a time-reversal vector stores one representative per pair).  hf_en plays no part and is not compared.
- * Out of scope: fries_rdm1 over ranks, time-reversal vectors, Hubbard-Holstein, the importance-weighted
+ * Over ranks: fries_rdm1_ranks below.  Out of scope: time-reversal vectors, Hubbard-Holstein, the importance-weighted
  * compression of observables_mol (weight_vec, --exponent), a binding in include/FRIES, and replicas for drivers other than frisys_mol_hip. */
 typedef struct { double ovlp, abs_sum; uint64_t n_src, n_terms, n_hits; } fries_rdm1_result;
 int fries_rdm1(fries_ctx *a, fries_ctx *b, double *gamma /* n_orb * n_orb, row-major */, fries_rdm1_result *out);
@@ -363,10 +364,67 @@ int fries_rdm1(fries_ctx *a, fries_ctx *b, double *gamma /* n_orb * n_orb, row-m
  * Hubbard-Holstein context, a context with a communicator, contexts on different devices or that differ in n_orb, n_elec or irreps, and
  * spin_parity != 0 on either side.  hf_en is not compared.  Refused after the counting pass, before any record is written: 32 positions
  * whose records exceed the capacity, and scratch that exceeds the free device memory.
- * Out of scope: ranks, time-reversal vectors, Hubbard-Holstein, three-body quantities, the importance-weighted compression of
+ * Over ranks: fries_rdm2_ranks below.  Out of scope: time-reversal vectors, Hubbard-Holstein, three-body quantities, the importance-weighted compression of
  * observables_mol, a binding in include/FRIES, replicas for other drivers, and skipping probes by point-group symmetry. */
 typedef struct { double ovlp, abs_sum; uint64_t n_src, n_terms, n_hits; } fries_rdm2_result;
 int fries_rdm2(fries_ctx *a, fries_ctx *b, double *gamma2 /* n_orb^4, row-major */, fries_rdm2_result *out);
+
+/* ---- Vector snapshots, and the three estimators over ranks.
+ * A snapshot is an immutable, device-resident copy of column 0 of a solution vector, sharded over ranks or not: the shards' live
+ * entries (value != 0) as one (determinant, value) list -- every shard's entries in position order, the shards in rank order, so the
+ * content is a function of the vectors alone -- and one open-addressed look-up table over the list (16-byte slots, linear probing, at
+ * most 40 % full, at least 2^14 slots: the layout and the hash of the vector's own table).  It is what the probed side `b` of
+ * fries_h_dot, fries_rdm1 and fries_rdm2 needs and nothing more: those kernels read b's table and b's values only.  A snapshot outlives
+ * whatever its source does next (iterate it, destroy it): it is built once per meeting of the replicas and serves all three estimators
+ * and every partner that probes that replica.
+ * fries_snapshot_create: a stable compaction on every shard's own stream, a copy of the lists to `device` (hipMemcpyPeerAsync; an
+ * ordinary copy where the devices are equal), one insert kernel there (64-bit compare-and-swap on the key, plain store of the
+ * position).  The call returns after a synchronisation: nothing reads the table before, and later users need no cross-stream wait.
+ * All device memory is sized from the shards' curr_size and checked against the free memory of every device involved before
+ * anything is allocated or launched; the staging is freed before the call returns, the rest belongs to the snapshot until
+ * fries_snapshot_destroy (a null snapshot is left alone).  The shards are only read.
+ * Refused with a message that names fries_snapshot_create and without a launch: a null argument; n_shards of 0 or above 64; a
+ * Hubbard-Holstein context; a context without a molecule or without a solution vector; shards that are not exactly ranks
+ * 0 .. n_shards - 1 of one run, in order (a context's communicator has another size than n_shards, entry k is not rank k, or the
+ * contexts' rank scramblers or iteration counts differ: what determines a run's content -- a context without a communicator is the
+ * one shard of a run of one); shards that differ in n_orb,
+ * n_elec, irreps, hf_en or spin_parity; a device index out of range; more than 2^32 - 2 positions.  Refused after the insert: a
+ * determinant that two shards hold or that is no valid key, a full table.
+ * Threads: one host thread makes the call, and no context among the shards may be inside another call meanwhile.  The calls of this
+ * section select devices of their own and put the calling thread's current device back before they return.
+ * The fill follows FRIES_HASH_FILL where it is set, as the vector's own table does (default 40).
+ * fries_snapshot_info: n_entries, the number of shards, the table's slots, the device bytes the snapshot owns, its device, and -- only
+ * where FRIES_SNAPSHOT_EVENTS=1 was set when the library first built a snapshot, otherwise 0 -- what the three steps of the build took on
+ * the device (HIP events; the compaction summed over the shards' streams).
+ * fries_snapshot_vector: the entries in the snapshot's order (rank-major, position order within a rank); *n = n_entries even when cap is
+ * too small (the call then fails); dets or vals may be NULL. */
+typedef struct fries_snapshot fries_snapshot;
+typedef struct { uint64_t n_entries; uint32_t n_shards, n_slots; uint64_t device_bytes; int32_t device; float ms_compact, ms_copy, ms_insert; } fries_snapshot_info_t;
+int fries_snapshot_create(fries_snapshot **s, fries_ctx *const *shards, uint32_t n_shards, int device);
+int fries_snapshot_info(const fries_snapshot *s, fries_snapshot_info_t *out);
+int fries_snapshot_vector(const fries_snapshot *s, uint64_t *dets, double *vals, uint64_t cap, uint64_t *n);
+int fries_snapshot_destroy(fries_snapshot *s);
+/* fries_h_dot, fries_rdm1 and fries_rdm2 with the enumerating side `a` given as the n_a shards of one run and the probed side `b` as a
+ * snapshot: the unchanged kernels of the two-context calls run once per shard of `a`, on that shard's stream, against the snapshot's
+ * table, one shard after the other (an empty shard launches nothing), and the shards' results are added on the host in rank order --
+ * the scalars and the counts, every bin of gamma, every bin of gamma2 after each shard's own symmetrisation, so that
+ * gamma2[p][q][r][s] == gamma2[r][s][p][q] stays bit for bit.  The results are those of the two-context calls on the unions of the
+ * shards up to the association order of the sums: the counts are equal, and with one shard per side every bit is.  Deterministic: two
+ * calls on the same shards and snapshot return the same bits.  `a` is only read; a snapshot of `a` itself may be passed as `b`.
+ * Refused with a message that names the entry point and before the first launch: a null argument; `a` failing the completeness rule of
+ * fries_snapshot_create; a shard of `a` on another device than the snapshot; another molecule than the snapshot's (n_orb, n_elec,
+ * irreps); for fries_h_dot_ranks a differing hf_en or spin_parity; for the density matrices spin_parity != 0 on either side or more
+ * than 32 orbitals.  What a shard's positions need in bin records is known only after its counting pass, as in fries_rdm2: fries_rdm2_ranks
+ * runs every shard's counting pass (one launch per non-empty shard) and refuses a capacity (FRIES_RDM2_RECORDS) below any workgroup's need,
+ * naming the shard, before a single record is written; gamma2 and *out are then left zero.  The scratch of a shard's records is checked
+ * against the free memory when that shard's turn comes.
+ * Threads: one host thread makes the call; no context of `a` may be inside another call on another thread meanwhile, and the snapshot
+ * must not be destroyed.  Several threads may probe one snapshot at the same time with different `a`.
+ * Out of scope: ranks in separate processes (a snapshot needs all shards in one process), frisys_mol_hip --replicas with --ranks,
+ * time-reversal vectors in the density matrices, Hubbard-Holstein, the other drivers.  No run on more than one GPU has been made. */
+int fries_h_dot_ranks(fries_ctx *const *a, uint32_t n_a, const fries_snapshot *b, fries_hdot_result *out);
+int fries_rdm1_ranks(fries_ctx *const *a, uint32_t n_a, const fries_snapshot *b, double *gamma /* n_orb * n_orb */, fries_rdm1_result *out);
+int fries_rdm2_ranks(fries_ctx *const *a, uint32_t n_a, const fries_snapshot *b, double *gamma2 /* n_orb^4 */, fries_rdm2_result *out);
 
 /* The hot-path operators one by one, on the context's solution vector. */
 /* apply_HBPP_sys (heat_bathPP.cpp:686-992) with the five uniforms it would draw; outputs as
