@@ -524,6 +524,20 @@ extern "C" int fries_h_dot_ranks(fries_ctx *const *a, uint32_t n_a, const fries_
         fr_h_dot_ranks(c.data(), n_a, b, out);
     });
 }
+// column += coeff * snapshot, and the plain overlap with a snapshot: snapshot.hip
+extern "C" int fries_vec_axpy_snapshot(fries_ctx *h, int column, double coeff, const fries_snapshot *x, uint64_t *n_taken) {
+    return fr_api([&] {
+        if (!h || !x || !n_taken) throw FriesError("fries_vec_axpy_snapshot: null argument");
+        fr_vec_axpy_snapshot(&h->c, column, coeff, x, n_taken);
+    });
+}
+extern "C" int fries_snapshot_dot(fries_ctx *const *a, uint32_t n_a, int column, const fries_snapshot *b, fries_vdot_result *out) {
+    return fr_api([&] {
+        if (!b || !out) throw FriesError("fries_snapshot_dot: null argument");
+        const std::vector<FriesCtx *> c = shard_list("fries_snapshot_dot", a, n_a);
+        fr_snapshot_dot(c.data(), n_a, column, b, out);
+    });
+}
 extern "C" int fries_rdm1_ranks(fries_ctx *const *a, uint32_t n_a, const fries_snapshot *b, double *gamma, fries_rdm1_result *out) {
     return fr_api([&] {
         if (!b || !gamma || !out) throw FriesError("fries_rdm1_ranks: null argument");

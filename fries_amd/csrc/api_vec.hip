@@ -1,6 +1,7 @@
 // The extern "C" boundary of the solution vector (include/fries_hip.h): what a host that keeps DistVec's pointer semantics reads, writes and
 // adds, matrix elements by the batch and H applied to a list -- with the kernels only these entry points launch.
 #include "api.hpp"
+#include "pair_frame.hpp"
 
 // at most 2048 workgroups for the grid-stride kernels over the stored positions
 static inline unsigned vec_grid(size_t m) { const unsigned nb = fr_blocks(m, FR_BLOCK); return nb > 2048 ? 2048 : nb; }
@@ -120,6 +121,48 @@ extern "C" int fries_vec_diag_download(fries_ctx *h, double *out, size_t cap, si
             FR_HIP(hipStreamSynchronize(c->stream));
             FR_HIP(hipMemcpy(out, c->vec.diag, 8 * m, hipMemcpyDeviceToHost));
         }
+    });
+}
+// ---- a scale and a one-norm of a column (include/fries_hip.h: beside fries_vec_axpy_snapshot)
+// what both refuse, by name and before anything is launched: the single-context frame of pair_frame.hpp
+static void need_mol_vec(const char *who, const fries_ctx *h, int column) {
+    const std::string w = std::string(who) + ": ";
+    if (!h) throw FriesError(w + "null argument");
+    fr_ctx_check(w, &h->c);
+    fr_column_check(w, column);
+}
+// two positions per step where the pair is whole (the columns are 16-byte aligned), the odd last one on its own
+__global__ void __launch_bounds__(FR_BLOCK) k_vec_scale(VecDev V, int column, double f) {
+    const uint32_t n = V.st->curr_size < V.cap ? V.st->curr_size : V.cap, n2 = n >> 1;
+    double *a = column ? V.v1 : V.v0;
+    double2 *a2 = (double2 *)a;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (size_t)gridDim.x * blockDim.x) {
+        double2 x = a2[i];
+        x.x *= f; x.y *= f;
+        a2[i] = x;
+    }
+    if ((n & 1u) && blockIdx.x == 0 && threadIdx.x == 0) a[n - 1] *= f;
+}
+extern "C" int fries_vec_scale(fries_ctx *h, int column, double factor) {
+    return fr_api([&] {
+        need_mol_vec("fries_vec_scale", h, column);
+        FriesCtx *c = &h->c;
+        FR_HIP(hipSetDevice(c->device));
+        fr_vec_sync_state(c, &c->vec, &c->h_vst);
+        const uint32_t m = c->h_vst.curr_size;
+        c->comp_pending = false;        // a compression result left on the device was formed from the values as they stood
+        if (m) FR_LAUNCH(c, "k_vec_scale", k_vec_scale, dim3(vec_grid((m + 1) / 2)), dim3(FR_BLOCK), c->vec, column, factor);
+    });
+}
+extern "C" int fries_vec_one_norm(fries_ctx *h, int column, double *norm) {
+    return fr_api([&] {
+        need_mol_vec("fries_vec_one_norm", h, column);
+        if (!norm) throw FriesError("fries_vec_one_norm: null argument");
+        FriesCtx *c = &h->c;
+        if (!c->vc.seq.total) throw FriesError("fries_vec_one_norm: the context has no compression scratch for the in-order sum (run a setup first)");
+        FR_HIP(hipSetDevice(c->device));
+        fr_vec_sync_state(c, &c->vec, &c->h_vst);
+        *norm = fr_one_norm(c, column);
     });
 }
 // DistVec::dot(idx2, vals2, num2, hashes2) (vec_utils.hpp:228-238): sum over the list IN LIST ORDER of vals2[i] * v[column][pos(idx2[i])],

@@ -402,13 +402,29 @@ __global__ void __launch_bounds__(FR_BLOCK) k_mc_walk(VecDev V, VcompBuf B, uint
     }
 }
 // exact in-order sum of |v| over the stored vector (DistVec::local_norm), to the host
-double fr_abs_norm(FriesCtx *c) {
+double fr_abs_norm(FriesCtx *c, int column) {
     const uint32_t bound = c->h_vst.curr_size ? c->h_vst.curr_size : 1;
-    AccAbs aa{c->vec.v0, c->vec.st};
+    AccAbs aa{column ? c->vec.v1 : c->vec.v0, c->vec.st};
     run_seq(c, c->vc.seq, aa, bound);
     double t = 0;
     FR_HIP(hipMemcpyAsync(&t, c->vc.seq.total, 8, hipMemcpyDeviceToHost, c->stream));
     FR_HIP(hipStreamSynchronize(c->stream));
+    return t;
+}
+// DistVec::local_norm + sum_mpi (fries_vec_one_norm): this rank's in-order sum, then the ranks' sums in rank order (one all-gather).
+// The host copy of the vector's state must be current.
+double fr_one_norm(FriesCtx *c, int column) {
+    if (!c->use_comm) return fr_abs_norm(c, column);
+    const uint32_t bound = c->h_vst.curr_size ? c->h_vst.curr_size : 1;
+    AccAbs aa{column ? c->vec.v1 : c->vec.v0, c->vec.st};
+    run_seq(c, c->vc.seq, aa, bound);
+    FR_LAUNCH(c, "k_put_double", k_put_double, dim3(1), dim3(1), c->vc.seq.total, (double *)c->comm.small_send);
+    const double *all = (const double *)fr_allgather(c, sizeof(double));
+    double h[FR_MAX_RANKS];
+    FR_HIP(hipMemcpyAsync(h, all, 8 * (size_t)c->n_ranks, hipMemcpyDeviceToHost, c->stream));
+    FR_HIP(hipStreamSynchronize(c->stream));
+    double t = 0;
+    for (int p = 0; p < c->n_ranks; p++) t += h[p];
     return t;
 }
 void fr_multi_walks(FriesCtx *c, double rn, double prev_glob_norm, uint32_t n_teeth, uint32_t *n_walk, double *unit_out) {

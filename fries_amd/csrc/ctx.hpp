@@ -318,7 +318,8 @@ void fr_dots(FriesCtx *c, double *numer, double *denom);
 const void *fr_dots_enqueue(FriesCtx *c);
 void fr_dots_collect(FriesCtx *c, const void *h_d, double *numer, double *denom);
 void fr_unkept_norm(FriesCtx *c, uint32_t bound);
-double fr_abs_norm(FriesCtx *c);
+double fr_abs_norm(FriesCtx *c, int column = 0);
+double fr_one_norm(FriesCtx *c, int column);
 void fr_multi_walks(FriesCtx *c, double rn, double prev_glob_norm, uint32_t n_teeth, uint32_t *n_walk, double *unit_out);
 // pivotal.hip
 void fr_piv_flat_reserve(FriesCtx *c, DevMem &m, uint32_t cap);
@@ -371,3 +372,5 @@ void fr_snapshot_destroy(fries_snapshot *s);
 void fr_h_dot_ranks(FriesCtx *const *a, uint32_t n_a, const fries_snapshot *b, fries_hdot_result *out);
 void fr_rdm1_ranks(FriesCtx *const *a, uint32_t n_a, const fries_snapshot *b, double *gamma, fries_rdm1_result *out);
 void fr_rdm2_ranks(FriesCtx *const *a, uint32_t n_a, const fries_snapshot *b, double *gamma2, fries_rdm2_result *out);
+void fr_vec_axpy_snapshot(FriesCtx *c, int column, double coeff, const fries_snapshot *x, uint64_t *n_taken);
+void fr_snapshot_dot(FriesCtx *const *a, uint32_t n_a, int column, const fries_snapshot *b, fries_vdot_result *out);

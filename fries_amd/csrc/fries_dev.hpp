@@ -305,6 +305,19 @@ __device__ __forceinline__ unsigned long long fr_hh_hash(det_t d, const uint32_t
     }
     return hash;
 }
+// DistVec::idx_to_proc (vec_utils.hpp:360-379): the rank that owns a determinant (vec.hip: the spawn exchange; snapshot.hip: fries_vec_axpy_snapshot)
+__device__ __forceinline__ uint32_t fr_proc_of(det_t d, const uint32_t *scr, uint32_t n_ranks) {
+    unsigned long long hash = 0;
+    uint32_t i = 0;
+    while (d) {
+        unsigned orb = __ffsll((long long)d) - 1;
+        d &= d - 1;
+        uint32_t term = (i + 1u) * scr[orb];             // unsigned int * uint32_t: wraps at 32 bits (det_hash.hpp:160-170)
+        hash = 1099511628211ULL * hash + term;
+        i++;
+    }
+    return (uint32_t)(hash % n_ranks);
+}
 // What identifies a stored index.  Molecules: the determinant.  Hubbard-Holstein: what the reference's HashTable can tell
 // apart -- the bucket (hash % table size) and the first ceil(2 n_sites / 8) bytes (det_hash.hpp:47, :60-94): states with
 // the same electrons, different phonons and the same bucket share one entry there, and so they do here.

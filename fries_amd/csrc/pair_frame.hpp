@@ -48,18 +48,23 @@ static inline uint32_t fr_pair_begin_rdm(const char *who, FriesCtx *a, FriesCtx 
         if (c->spin_parity != 0) throw FriesError(w + "a context with spin_parity != 0 stores one representative per time-reversal pair; unfolding it is out of scope");
     return n_pos;
 }
+// What every entry point that reads or writes the solution vector of a molecular context refuses of that context, before it launches
+// anything (fr_shards_check below; fries_vec_axpy_snapshot in snapshot.hip; fries_vec_scale and fries_vec_one_norm in api_vec.hip).  w = "<entry point>: "
+static inline void fr_ctx_check(const std::string &w, const FriesCtx *c) {
+    if (c->hh_mode || c->vec.hh_sites) throw FriesError(w + "a Hubbard-Holstein context is not a molecular one (out of scope)");
+    if (!c->d_eris || !c->d_hb) throw FriesError(w + "fries_set_molecule must be called on every context first");
+    if (!c->vec.dets || !c->vec.hs) throw FriesError(w + "every context needs a solution vector (run a setup first)");
+}
+static inline void fr_column_check(const std::string &w, int column) {
+    if (column != 0 && column != 1) throw FriesError(w + "column must be 0 or 1");
+}
 // What a list of contexts must be to stand for ONE vector (fries_snapshot_create, the *_ranks estimators; snapshot.hip): molecular contexts
 // with a solution vector that are exactly ranks 0 .. n - 1 of one run, in order, and agree in everything the estimators compare.  A context
 // without a communicator is the one shard of a run of one.  "One run" is decided by what determines a run's content: the rank scramblers
 // (drawn from the seed) and the iteration count -- two groups set up alike and iterated alike hold the same shards, bit for bit.
 static inline void fr_shards_check(const char *who, FriesCtx *const *sh, uint32_t n) {
     const std::string w = std::string(who) + ": ";
-    for (uint32_t k = 0; k < n; k++) {
-        const FriesCtx *c = sh[k];
-        if (c->hh_mode || c->vec.hh_sites) throw FriesError(w + "a Hubbard-Holstein context is not a molecular one (out of scope)");
-        if (!c->d_eris || !c->d_hb) throw FriesError(w + "fries_set_molecule must be called on every context first");
-        if (!c->vec.dets || !c->vec.hs) throw FriesError(w + "every context needs a solution vector (run a setup first)");
-    }
+    for (uint32_t k = 0; k < n; k++) fr_ctx_check(w, sh[k]);
     const FriesCtx *c0 = sh[0];
     for (uint32_t k = 0; k < n; k++) {
         const FriesCtx *c = sh[k];

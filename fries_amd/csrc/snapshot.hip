@@ -9,10 +9,14 @@
 //   3. insert: k_snap_insert puts entry i under its determinant as k_hash_reinsert does -- fr_hash_slot, a 64-bit atomicCAS on the key,
 //      linear probing, a plain store of the position.  Which slot a key ends in can depend on timing where two keys collide; what a
 //      look-up returns cannot: every key is in the table once and hd_resolve probes until it finds it or an empty slot.
+// Two more calls read a snapshot (below the estimators): fries_vec_axpy_snapshot adds coeff * snapshot into a context's vector -- the entries
+// the context owns, filtered into its spawn buffers by the same count / scan / write and merged like any perform_add --, and
+// fries_snapshot_dot is the plain overlap of a sharded vector with it, one look-up per position.
 // Nothing reads the table before fr_snapshot_create has synchronised.  The sizes follow from the shards' curr_size (snapshot_plan.hpp)
 // and are checked against the free memory of every device involved before the first allocation.
 #include "ctx.hpp"
 #include "snapshot_plan.hpp"
+#include "axpy_plan.hpp"
 #include "pair_frame.hpp"
 #include <map>
 #include <memory>
@@ -327,5 +331,174 @@ void fr_rdm2_ranks(FriesCtx *const *a, uint32_t n_a, const fries_snapshot *b, do
         for (size_t j = 0; j < n4; j++) gamma2[j] += g[j];
         out->ovlp += r[k].ovlp; out->abs_sum += r[k].abs_sum;
         out->n_src += r[k].n_src; out->n_terms += r[k].n_terms; out->n_hits += r[k].n_hits;
+    }
+}
+
+// ------------------------------------------------------------------ column += coeff * snapshot (fries_vec_axpy_snapshot)
+static_assert(AXPY_TILE == 4 * FR_BLOCK && AXPY_TILE == SNAP_TILE, "a thread holds 4 contiguous entries of its tile");
+static_assert(AXPY_MAX_TILES <= FR_MAX_PART, "the tiles' counts live in SpawnBuf::pcnt");
+// thread t of tile b holds entries b * AXPY_TILE + 4 t .. + 3 of the chunk -> their determinants and products fl(coeff * x), 0 past the
+// end and for an entry another rank owns; and how many are taken (a product of 0 is dropped, as HostAdds drops zero values)
+__device__ __forceinline__ uint32_t axpy_load4(const det_t *dets, const double *vals, uint32_t n, double coeff, const uint32_t *scr, uint32_t n_ranks, uint32_t rank,
+                                               det_t d[4], double p[4]) {
+    const size_t i0 = (size_t)blockIdx.x * AXPY_TILE + 4 * (size_t)threadIdx.x;
+    const bool al16 = (((uintptr_t)dets | (uintptr_t)vals) & 15u) == 0;      // a chunk starts at a multiple of the spawn capacity, which may be odd
+    if (i0 + 4 <= n && al16) {
+        const double2 x = *(const double2 *)(vals + i0), y = *(const double2 *)(vals + i0 + 2);
+        const ulonglong2 a = *(const ulonglong2 *)(dets + i0), b = *(const ulonglong2 *)(dets + i0 + 2);
+        p[0] = x.x; p[1] = x.y; p[2] = y.x; p[3] = y.y;
+        d[0] = a.x; d[1] = a.y; d[2] = b.x; d[3] = b.y;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++) { const bool in = i0 + j < n; p[j] = in ? vals[i0 + j] : 0.0; d[j] = in ? dets[i0 + j] : 0ull; }
+    }
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        p[j] = coeff * p[j];
+        if (p[j] != 0 && n_ranks > 1 && fr_proc_of(d[j], scr, n_ranks) != rank) p[j] = 0.0;
+        c += (uint32_t)(p[j] != 0);
+    }
+    return c;
+}
+__global__ void __launch_bounds__(FR_BLOCK) k_axpy_count(const det_t *dets, const double *vals, uint32_t n, double coeff, const uint32_t *scr, uint32_t n_ranks, uint32_t rank,
+                                                         uint32_t *tile_cnt) {
+    __shared__ uint32_t sh[4];
+    det_t d[4]; double p[4];
+    const uint32_t c = fr_block_sum_u32(axpy_load4(dets, vals, n, coeff, scr, n_ranks, rank, d, p), sh);
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = c;
+}
+// the taken entries in list order into the spawn list, every one with the initiator flag; out_* hold n entries and an offset is below
+// the number of taken entries, so below n
+__global__ void __launch_bounds__(FR_BLOCK) k_axpy_write(const det_t *dets, const double *vals, uint32_t n, double coeff, const uint32_t *scr, uint32_t n_ranks, uint32_t rank,
+                                                         const uint32_t *tile_off, det_t *out_det, double *out_val, uint8_t *out_ini) {
+    __shared__ uint32_t sh[4];
+    det_t d[4]; double p[4];
+    const uint32_t c = axpy_load4(dets, vals, n, coeff, scr, n_ranks, rank, d, p);
+    uint32_t tot;
+    uint32_t o = tile_off[blockIdx.x] + fr_block_scan_u32(c, sh, &tot) - c;
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        if (p[j] != 0 && o < n) { out_det[o] = d[j]; out_val[o] = p[j]; out_ini[o] = 1; o++; }
+}
+
+// what fries_vec_axpy_snapshot and fries_snapshot_dot refuse of a context (list) against a snapshot, beyond fr_shards_check's own
+static void snap_match(const std::string &w, const FriesCtx *c, const fries_snapshot *b) {
+    if (c->device != b->device) throw FriesError(w + "the context and the snapshot are on different devices");
+    if (c->n_orb != b->n_orb || c->n_elec != b->n_elec) throw FriesError(w + "the context and the snapshot differ in n_orb or n_elec (different molecules)");
+    if (memcmp(c->h_hb.irrep, b->irrep, c->n_orb)) throw FriesError(w + "the context and the snapshot differ in their orbital irreps (different molecules)");
+    if (c->spin_parity != b->spin_parity) throw FriesError(w + "the context and the snapshot differ in spin_parity");
+}
+
+void fr_vec_axpy_snapshot(FriesCtx *c, int column, double coeff, const fries_snapshot *x, uint64_t *n_taken) {
+    const std::string w = "fries_vec_axpy_snapshot: ";
+    // one shard of a run, with or without a communicator: fr_ctx_check, not fr_shards_check's completeness rule
+    fr_ctx_check(w, c);
+    if (!c->sp.det) throw FriesError(w + "the context has no spawn buffers (run a setup first)");
+    fr_column_check(w, column);
+    snap_match(w, c, x);
+    if (c->n_ranks > 1 && !c->d_proc_scr) throw FriesError(w + "a context of several ranks without its rank scrambler (run a setup first)");
+    *n_taken = 0;
+    if (coeff == 0 || x->n_entries == 0) return;
+    const AxpyPlan plan = fr_axpy_plan(x->n_entries, c->sp.cap);
+    if (plan.refused) throw FriesError(w + "the context's spawn capacity cannot stage a chunk");
+    FR_HIP(hipSetDevice(c->device));
+    SpawnBuf &S = c->sp;
+    uint32_t *tile_cnt = S.pcnt, *tile_off = S.flag;        // [n_tiles] each: n_tiles <= AXPY_MAX_TILES and <= the chunk's entries <= S.cap
+    const uint32_t n_ranks = c->use_comm ? (uint32_t)c->n_ranks : 1u;
+    uint64_t taken = 0;
+    for (const AxpyChunk &k : plan.chunk) {
+        fr_vec_sync_state(c, &c->vec, &c->h_vst);
+        fr_vec_maybe_rebuild(c, &c->vec);           // tombstones of earlier deletes, as fries_vec_add_to
+        const det_t *dets = x->dets + k.off; const double *vals = x->vals + k.off;
+        FR_LAUNCH(c, "k_axpy_count", k_axpy_count, dim3(k.n_tiles), dim3(FR_BLOCK), dets, vals, k.n, coeff, (const uint32_t *)c->d_proc_scr, n_ranks, (uint32_t)c->rank, tile_cnt);
+        FR_LAUNCH(c, "k_snap_scan", k_snap_scan, dim3(1), dim3(FR_BLOCK), (const uint32_t *)tile_cnt, k.n_tiles, tile_off, S.n_spawn);
+        FR_LAUNCH(c, "k_axpy_write", k_axpy_write, dim3(k.n_tiles), dim3(FR_BLOCK), dets, vals, k.n, coeff, (const uint32_t *)c->d_proc_scr, n_ranks, (uint32_t)c->rank,
+                  (const uint32_t *)tile_off, S.det, S.val, S.ini);
+        uint32_t m = 0;
+        FR_HIP(hipMemcpyAsync(&m, S.n_spawn, 4, hipMemcpyDeviceToHost, c->stream));
+        FR_HIP(hipStreamSynchronize(c->stream));
+        if (m > k.n) throw FriesError(w + "more entries taken than the chunk holds");
+        if (m) fr_vec_merge(c, &c->vec, m, column == 0);
+        taken += m;
+    }
+    *n_taken = taken;
+    fr_vec_sync_state(c, &c->vec, &c->h_vst);
+    fr_check_dev_err(c);
+}
+
+// ------------------------------------------------------------------ <a|snapshot> (fries_snapshot_dot)
+// One workgroup per tile of AXPY_TILE positions of the shard; a thread takes 4 contiguous positions, issues the first probes of those
+// with a non-zero value together and resolves them afterwards (hd_resolve).  No floating-point atomics: a thread adds its products in
+// position order, fr_block_sum combines the lanes of a wave by the fixed butterfly and the four waves in order, and the tiles' partials
+// are added in tile order on the host -- the association order is a function of curr_size alone.
+__global__ void __launch_bounds__(FR_BLOCK) k_snap_dot(const det_t *dets, const double *col, uint32_t n, VecDev B, double *p_dot, double *p_abs, uint32_t *p_src, uint32_t *p_hits) {
+    __shared__ double shd[4];
+    __shared__ uint32_t shu[4];
+    double v[4];
+    uint32_t n_src = snap_load4(col, n, v), n_hits = 0;
+    const size_t i0 = (size_t)blockIdx.x * AXPY_TILE + 4 * (size_t)threadIdx.x;
+    det_t d[4]; uint32_t sl[4]; HSlot e[4];
+    if (i0 + 4 <= n) {
+        const ulonglong2 a = *(const ulonglong2 *)(dets + i0), b = *(const ulonglong2 *)(dets + i0 + 2);
+        d[0] = a.x; d[1] = a.y; d[2] = b.x; d[3] = b.y;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++) d[j] = i0 + j < n ? dets[i0 + j] : 0ull;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        sl[j] = fr_hash_slot(d[j], B.hcap);
+        e[j].key = FR_EMPTY_KEY; e[j].val = FR_NOPOS;
+        if (v[j] != 0) e[j] = B.hs[sl[j]];
+    }
+    double acc = 0, ab = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (v[j] == 0) continue;
+        const double bv = hd_resolve(B, d[j], sl[j], e[j]);
+        if (bv != 0) { const double t = v[j] * bv; acc += t; ab += fabs(t); n_hits++; }
+    }
+    acc = fr_block_sum(acc, shd); ab = fr_block_sum(ab, shd);
+    n_src = fr_block_sum_u32(n_src, shu); n_hits = fr_block_sum_u32(n_hits, shu);
+    if (threadIdx.x == 0) { p_dot[blockIdx.x] = acc; p_abs[blockIdx.x] = ab; p_src[blockIdx.x] = n_src; p_hits[blockIdx.x] = n_hits; }
+}
+
+void fr_snapshot_dot(FriesCtx *const *a, uint32_t n_a, int column, const fries_snapshot *b, fries_vdot_result *out) {
+    const char *who = "fries_snapshot_dot";
+    const std::string w = std::string(who) + ": ";
+    DeviceGuard dg;
+    fr_shards_check(who, a, n_a);
+    fr_column_check(w, column);
+    for (uint32_t k = 0; k < n_a; k++) snap_match(w, a[k], b);
+    FR_HIP(hipSetDevice(b->device));
+    std::vector<uint32_t> n_pos(n_a);
+    for (uint32_t k = 0; k < n_a; k++) n_pos[k] = fr_pair_n_pos(w, a[k]);
+    *out = fries_vdot_result{};
+    const VecDev B = b->view();
+    // every shard's pass on its own stream, then the shards' partials in rank order
+    DevMem tmp;
+    std::vector<VdotPlan> plan(n_a);
+    std::vector<uint8_t *> base(n_a, nullptr);
+    for (uint32_t k = 0; k < n_a; k++) {
+        if (!n_pos[k]) continue;
+        FriesCtx *c = a[k];
+        const VdotPlan &g = plan[k] = fr_vdot_plan(n_pos[k]);
+        uint8_t *p = base[k] = tmp.alloc<uint8_t>(g.bytes);
+        FR_LAUNCH(c, "k_snap_dot", k_snap_dot, dim3(g.n_tiles), dim3(FR_BLOCK), (const det_t *)c->vec.dets, (const double *)(column ? c->vec.v1 : c->vec.v0), n_pos[k], B,
+                  (double *)(p + g.dot), (double *)(p + g.abs_sum), (uint32_t *)(p + g.n_src), (uint32_t *)(p + g.n_hits));
+    }
+    std::vector<uint8_t> h;
+    for (uint32_t k = 0; k < n_a; k++) {
+        if (!n_pos[k]) continue;
+        const VdotPlan &g = plan[k];
+        h.resize(g.bytes);
+        FR_HIP(hipMemcpyAsync(h.data(), base[k], g.bytes, hipMemcpyDeviceToHost, a[k]->stream));
+        FR_HIP(hipStreamSynchronize(a[k]->stream));
+        const double *hd = (const double *)(h.data() + g.dot), *ha = (const double *)(h.data() + g.abs_sum);
+        const uint32_t *hs = (const uint32_t *)(h.data() + g.n_src), *hh = (const uint32_t *)(h.data() + g.n_hits);
+        double dot = 0, ab = 0;
+        for (uint32_t t = 0; t < g.n_tiles; t++) { dot += hd[t]; ab += ha[t]; out->n_src += hs[t]; out->n_hits += hh[t]; }
+        out->dot += dot; out->abs_sum += ab;
     }
 }

@@ -566,19 +566,6 @@ void fr_vec_reserve_hash(FriesCtx *c, VecDev *v, uint32_t n_new) {
 // reference's accumulation order (pass 0 of every source before pass 1 of any).
 #define FR_XCH_MAXB (2 * FR_MAX_RANKS)
 
-__device__ __forceinline__ uint32_t fr_proc_of(det_t d, const uint32_t *scr, uint32_t n_ranks) {
-    unsigned long long hash = 0;
-    uint32_t i = 0;
-    while (d) {
-        unsigned orb = __ffsll((long long)d) - 1;
-        d &= d - 1;
-        uint32_t term = (i + 1u) * scr[orb];             // unsigned int * uint32_t: wraps at 32 bits (det_hash.hpp:160-170)
-        hash = 1099511628211ULL * hash + term;
-        i++;
-    }
-    return (uint32_t)(hash % n_ranks);
-}
-
 // bucket = 2 * destination + initiator flag; counts per 256-element tile
 #define FR_XCH_MAXR 1022    // perform_add rounds per pass when the Adder fills up
 // sel != nullptr: only the spawns of pass sel_pass whose index lies in round sel_round of this rank, [sel[r], sel[r + 1]) of

@@ -31,6 +31,7 @@ EXPORTS = [
     "fries_spawn_from_comp", "fries_dense_apply", "fries_dense_norm", "fries_dense_h_count", "fries_comp_download",
     "fries_h_dot", "fries_rdm1", "fries_rdm2",
     "fries_snapshot_create", "fries_snapshot_info", "fries_snapshot_vector", "fries_snapshot_destroy", "fries_h_dot_ranks", "fries_rdm1_ranks", "fries_rdm2_ranks",
+    "fries_vec_axpy_snapshot", "fries_snapshot_dot", "fries_vec_scale", "fries_vec_one_norm",
 ]
 
 
@@ -168,6 +169,20 @@ class Rdm2(NamedTuple):
         return float(-n_elec * (n_elec - 4) / 4.0 - 0.5 * np.einsum("pqqp->", self.gamma2) / self.ovlp)
 
 
+class VdotResult(C.Structure):
+    """struct fries_vdot_result"""
+    _fields_ = [("dot", C.c_double), ("abs_sum", C.c_double), ("n_src", C.c_uint64), ("n_hits", C.c_uint64)]
+
+
+class VDot(NamedTuple):
+    """fries_snapshot_dot's result: dot = <a|snapshot>, abs_sum = the sum of the magnitudes of its products; the positions of a with a
+    non-zero value and those of them found in the snapshot with a non-zero value."""
+    dot: float
+    abs_sum: float
+    n_src: int
+    n_hits: int
+
+
 class SnapshotInfoStruct(C.Structure):
     """struct fries_snapshot_info_t"""
     _fields_ = [("n_entries", C.c_uint64), ("n_shards", C.c_uint32), ("n_slots", C.c_uint32), ("device_bytes", C.c_uint64), ("device", C.c_int32),
@@ -296,6 +311,10 @@ def load_library() -> C.CDLL:
     lib.fries_h_dot_ranks.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(HdotResult)]
     lib.fries_rdm1_ranks.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Rdm1Result)]
     lib.fries_rdm2_ranks.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Rdm2Result)]
+    lib.fries_vec_axpy_snapshot.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.fries_snapshot_dot.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_int, C.c_void_p, C.POINTER(VdotResult)]
+    lib.fries_vec_scale.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    lib.fries_vec_one_norm.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
     _lib = lib
     return lib
 
@@ -654,6 +673,23 @@ class FriEngine:
         self._ck(self.lib.fries_rdm2(self.h, (self if other is None else other).h, _ptr(g), C.byref(r)))
         return Rdm2(g, r.ovlp, r.abs_sum, int(r.n_src), int(r.n_terms), int(r.n_hits))
 
+    def axpy_snapshot(self, column: int, coeff: float, snap) -> int:
+        """column[det] += coeff * snap[det] over the entries of the snapshot this engine owns (fries_vec_axpy_snapshot), merged on the
+        device like a vec_add_to of the same list with initiator flags 1; returns the number of entries merged."""
+        n = C.c_uint64()
+        self._ck(self.lib.fries_vec_axpy_snapshot(self.h, column, coeff, snap.h if snap is not None else None, C.byref(n)))
+        return int(n.value)
+
+    def scale(self, column: int, factor: float) -> None:
+        """v[column] *= factor over the stored positions (fries_vec_scale)"""
+        self._ck(self.lib.fries_vec_scale(self.h, column, factor))
+
+    def one_norm(self, column: int = 0) -> float:
+        """The sum of |v[column]| in position order, then over the ranks in rank order (fries_vec_one_norm; a collective with ranks)"""
+        out = C.c_double()
+        self._ck(self.lib.fries_vec_one_norm(self.h, column, C.byref(out)))
+        return out.value
+
     def variational_energy(self) -> float:
         """The Rayleigh quotient <v|H|v> / <v|v> of the current vector, on the scale of numer / denom."""
         r = self.h_dot()
@@ -704,6 +740,21 @@ class FriEngine:
         self._ck(self.lib.fries_apply_hbpp_piv(self.h, n_samp, int(unit_matrel), _ptr(pos), _ptr(orbs), _ptr(vals), cap, C.byref(m), _ptr(sl)))
         k = m.value
         return pos[:k].copy(), orbs[:k].copy(), vals[:k].copy(), sl
+
+    def apply_hbpp_piv_device(self, n_samp: int):
+        """apply_HBPP_piv with the result left on the device (for spawn_from_comp / comp_download); returns (num_success, stage_len[5])."""
+        m = C.c_size_t()
+        sl = np.zeros(5, dtype=np.uint32)
+        self._ck(self.lib.fries_apply_hbpp_piv(self.h, n_samp, 0, None, None, None, C.c_size_t(-1).value, C.byref(m), _ptr(sl)))
+        return m.value, sl
+
+    def dot_list(self, column: int, dets, vals) -> float:
+        """DistVec::dot: the sum over the list, in list order, of vals[i] * v[column][det_i] (fries_vec_dot_list)"""
+        d = np.ascontiguousarray(dets, dtype=np.uint64)
+        v = np.ascontiguousarray(vals, dtype=np.float64)
+        out = C.c_double()
+        self._ck(self.lib.fries_vec_dot_list(self.h, column, _ptr(d), _ptr(v), min(d.size, v.size), C.byref(out)))
+        return out.value
 
     def compress_vec(self, n_samp: int, rn: float):
         nk = C.c_uint32()
@@ -826,6 +877,13 @@ class VecSnapshot:
         r = HdotResult()
         self._ck(self.lib.fries_h_dot_ranks(arr, len(shards), self.h, C.byref(r)))
         return HDot(r.h, r.ovlp, r.abs_sum, int(r.n_src), int(r.n_terms), int(r.n_hits))
+
+    def dot(self, a_shards, column: int = 0) -> VDot:
+        """<a|snapshot> with `column` of a (fries_snapshot_dot): one look-up per stored position of a_shards, no Hamiltonian."""
+        shards, arr = _handles(a_shards)
+        r = VdotResult()
+        self._ck(self.lib.fries_snapshot_dot(arr, len(shards), column, self.h, C.byref(r)))
+        return VDot(r.dot, r.abs_sum, int(r.n_src), int(r.n_hits))
 
     def rdm1(self, a_shards) -> Rdm1:
         """The one-body density matrix <a| ... |snapshot> (fries_rdm1_ranks)"""

@@ -35,6 +35,8 @@ _SHAPES = {
     # of the determinant used), in two irreps; and the smallest closed shell with a choice to make (2 electrons in 4 orbitals)
     "MAX32": (6, "Cs", [0, 1] * 16),
     "MIN4": (2, "C1", [0, 0, 0, 0]),
+    # ... and one small enough for a dense eigensolver (225 determinants) with more than one irrep (fries_amd/subspace.py's tests)
+    "MIN6": (4, "Cs", [0, 1, 0, 1, 0, 1]),
 }
 
 

@@ -426,6 +426,35 @@ int fries_h_dot_ranks(fries_ctx *const *a, uint32_t n_a, const fries_snapshot *b
 int fries_rdm1_ranks(fries_ctx *const *a, uint32_t n_a, const fries_snapshot *b, double *gamma /* n_orb * n_orb */, fries_rdm1_result *out);
 int fries_rdm2_ranks(fries_ctx *const *a, uint32_t n_a, const fries_snapshot *b, double *gamma2 /* n_orb^4 */, fries_rdm2_result *out);
 
+/* ---- what a loop over several vectors needs beside the operators below (fries_amd/subspace.py: the reference's subsp_mol loop with one
+ * context per state): the one step that mixes vectors, a plain overlap, a scale and a one-norm.
+ * Each of the four refuses with a message that names it and before the first launch: a null argument; a Hubbard-Holstein context; a
+ * context without a molecule or without a solution vector; a column other than 0 or 1; a snapshot on another device than the context; a
+ * snapshot of another molecule (n_orb, n_elec, irreps) or spin_parity.
+ *
+ * fries_vec_axpy_snapshot: column[det] += coeff * x[det] for every entry of the snapshot that this context owns -- all of them without
+ * a communicator, those with idx_to_proc(det) == rank with one.  The whole snapshot is on the device, so the call is no collective and
+ * needs no exchange: every rank takes its own.  The product is rounded once, fl(coeff * x); an entry whose product is 0 is dropped, as
+ * DistVec::add drops zero values.  The rest are merged in the snapshot's order with initiator flag 1, as fries_vec_add_to merges a host
+ * list: a determinant not yet stored gets the position that call would give it, and a vector whose capacity (max_dets) the inserts
+ * would exceed is refused as there.  The owned entries are staged into the context's spawn buffers on the device (count, scan, write:
+ * nothing passes through the host), in chunks of at most the spawn capacity, one merge per chunk, in list order.  coeff == 0 or an empty
+ * snapshot returns at once without a launch.  *n_taken = the entries merged.  A pending compression result is cleared, as by any merge. */
+int fries_vec_axpy_snapshot(fries_ctx *ctx, int column, double coeff, const fries_snapshot *x, uint64_t *n_taken);
+/* fries_snapshot_dot: sum_i a_i * b(det_i) over the stored positions of the shards of `a` with a non-zero value in `column`, each looked
+ * up in the snapshot's table.  `a` follows the completeness rule of fries_snapshot_create.  One pass per shard on that shard's stream
+ * (an empty shard launches nothing); the shards are added on the host in rank order.  abs_sum = the sum of the magnitudes of the
+ * products, n_src = the positions with a non-zero value, n_hits = those found in the snapshot with a non-zero value.  No floating-point
+ * atomics: per-wave sums in a fixed order, one partial per 1024-position tile, the partials added in tile order; two calls on the same
+ * data return the same bits. */
+typedef struct { double dot, abs_sum; uint64_t n_src, n_hits; } fries_vdot_result;
+int fries_snapshot_dot(fries_ctx *const *a, uint32_t n_a, int column, const fries_snapshot *b, fries_vdot_result *out);
+/* v[column][i] *= factor over the stored positions */
+int fries_vec_scale(fries_ctx *ctx, int column, double factor);
+/* DistVec::local_norm + sum_mpi: the sum of |v[column][i]| in position order, then over the ranks in rank order.  With a communicator a
+ * collective (one all-gather). */
+int fries_vec_one_norm(fries_ctx *ctx, int column, double *norm);
+
 /* The hot-path operators one by one, on the context's solution vector. */
 /* apply_HBPP_sys (heat_bathPP.cpp:686-992) with the five uniforms it would draw; outputs as
  * comp_vecs.{det_indices2, orb_indices1, vec1}.  unit_matrel != 0 uses the |value| = 1 lambdas of
